@@ -13,10 +13,22 @@ every rank keeps 32 trajectories per step (global batch 32*N sharded by dist.Dat
 Inputs are synthetic and resident in HBM before the timed region, except the
 [B, 20, 2] trajectory coordinates that train_epoch receives on the host like the reference does.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields.  A plain run does only what they need: set-up (the step's
+hipGraph is captured), --warmup steps, EXACTLY --steps timed steps, the outputs (--dump-outputs DIR), the line.
+With --full the line also carries what takes runs of its own:
   roofline     : the dominant kernel (the MFMA conv), timed live with HIP events on the launch stream
                  in a separate instrumented step; achieved = algorithmic FLOPs / kernel time
-  cpu_baseline : the CPU oracle (torch-CPU restatement of the reference, "port") on a bounded sample.
+  step_roofline: the whole step against both roofs (the FLOPs counted in one extra eager step)
+  timed_regions (two repeats of the contract region) / sustained (a >= 5 s region of the same replayed steps)
+  c5, c1, c4   : short legs of the other BASELINE configurations (C2 on one GPU)
+  cpu_baseline : the CPU oracle (torch-CPU restatement of the reference, "port") on a bounded sample,
+                 with parity_check of the HIP path's first steps against it
+  world.allreduce_us_per_step / replayed_step_split_ms : the collective timed on its own (N > 1)
+The --no-* options trim a --full run.
+
+--dump-outputs DIR writes, after the timed steps, what the timed path returned to its caller in its last call and what it left
+in the model: loss.npy, ade.npy, fde.npy (float64; C5 also {ade,fde}_per_trajectory.npy) and, for the training configs, param.<name>.npy / grad.<name>.npy of every
+trainable tensor (float32: the weights after the last Adam step and that step's gradients).  All inputs are seeded.
 """
 import argparse
 import glob
@@ -514,6 +526,37 @@ def parity_check(first, gpu_steps, launched):
             "tolerance": {"loss_rel": 2e-5, "ade_fde_abs": 1e-4}, "ok": ok}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, ade, fde, loss, train, sweep=None):
+    """--dump-outputs: what the timed region's train_epoch / evaluate call returned (loss, ADE, FDE as float64; for the evaluation
+    sweep also its per-trajectory ADE / FDE) and, for a training step, what it left in the model: every trainable tensor after the
+    last Adam step and that step's gradient (float32).  Above
+    DUMP_LIMIT_BYTES in all, every large array is cut to a fixed, seeded sample of its elements (flat; the indices sorted)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.array([loss], dtype=np.float64), "ade": np.array([ade], dtype=np.float64),
+              "fde": np.array([fde], dtype=np.float64)}
+    if sweep is not None:
+        arrays["ade_per_trajectory"] = sweep["ade"].to_numpy(dtype=np.float64)
+        arrays["fde_per_trajectory"] = sweep["fde"].to_numpy(dtype=np.float64)
+    if train:
+        for name, p in model.named_parameters():
+            if p.requires_grad:
+                arrays["param." + name] = p.detach().float().cpu().numpy()
+                if p.grad is not None:
+                    arrays["grad." + name] = p.grad.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // (4 * len(arrays))      # elements per array
+        for k, a in arrays.items():
+            if a.size > share:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+                arrays[k] = a.reshape(-1)[idx]
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def step_roofline(value_per_gpu, gf, mb, executed_gflop_per_traj):
     """The whole step against both roofs (per GPU); the dominant kernel's figure is in "roofline"."""
     return {
@@ -551,7 +594,14 @@ def main():
     ap.add_argument("--no-sustained", action="store_true", help="skip the >= 5 s sustained region after the contract's timed region")
     ap.add_argument("--sustained-seconds", type=float, default=5.5)
     ap.add_argument("--layers", action="store_true", help="print one line per conv launch of the instrumented step (stderr)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: roofline, step_roofline, repeat and sustained regions, "
+                         "the C5 / C1 / C4 legs, the CPU baseline with its parity check, the collective on its own")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last call to DIR/<name>.npy")
     args = ap.parse_args()
+    if (args.layers or args.conv_layers) and not args.full:
+        ap.error("--layers / --conv-layers time the instrumented steps of a --full run")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Plain `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU over RCCL), as CHILD processes
@@ -624,9 +674,11 @@ def main():
         """The inputs of `n_steps` steps (host coordinates, as the reference's loader hands them over) -- generated BEFORE a timed region."""
         return loader_for(synthetic_trajectories(cfg, B * N * n_steps, H, W, seed))
 
+    last_sweep = {}
+
     def go(loader, graph=None):
         if args.config == "C5":
-            a, f, _, _ = ev.evaluate(model, loader, images, dev, "sdd", None, in_t, list(cfg.waypoints), "test",
+            a, f, last_sweep["df"], _ = ev.evaluate(model, loader, images, dev, "sdd", None, in_t, list(cfg.waypoints), "test",
                                      20, 1, cfg.obs_len, B * N, cfg.resize_factor, cfg.temperature, dp=dp)
             return a, f, 0.0
         return te.train_epoch(model, loader, images, opt, crit, cfg.loss_scale, dev, "sdd", None, gt_t, in_t,
@@ -662,11 +714,13 @@ def main():
     # step with concurrent branches; measured after it the same launches read ~5 % longer on a chip the denser captured
     # work has warmed up).  All ranks run them (collectives inside).
     # FLOPs the product really launches per step (one counted step; all ranks run it: collectives inside)
-    with FlopCounter(ops) as fc:
-        run(1, 4, graph=False)
-    executed_gflop_per_traj = fc.flops / B / 1e9      # (this rank's launches over this rank's B trajectories)
+    executed_gflop_per_traj = None
+    if args.full:
+        with FlopCounter(ops) as fc:
+            run(1, 4, graph=False)
+        executed_gflop_per_traj = fc.flops / B / 1e9      # (this rank's launches over this rank's B trajectories)
     ct, n_inst = None, 3
-    if not args.no_roofline and args.config != "C5":
+    if args.full and not args.no_roofline and args.config != "C5":
         ops.overlap_decoders = False      # kernels are timed in isolation: the two decoder streams run back to back
         run(1, 3, graph=False)            # (first launches: code objects, function attributes, allocator growth)
         if rank == 0:
@@ -691,14 +745,17 @@ def main():
         run(args.warmup, 1)
     elapsed, (ade, fde, loss) = timed(args.steps, 2, first_loader)
     value = B * N * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        # before anything else runs a step: the model still holds what the timed region's last step left in it
+        dump_outputs(args.dump_outputs, model, ade, fde, loss, train=args.config != "C5", sweep=last_sweep.get("df"))
     # The contract's timed region is the one above (EXACTLY --steps steps); two more identical regions give the spread
     regions = [elapsed / args.steps * 1e3]
-    for rep in range(0 if args.no_repeats else 2):
+    for rep in range(0 if (args.no_repeats or not args.full) else 2):
         regions.append(timed(args.steps, 5 + rep)[0] / args.steps * 1e3)
     # >= 5 s of the same replayed steps after the contract region: long enough for the driver's SMI sampler to see the GPU busy,
     # and a check of the clocks under sustained load (the contract region is 0.2-0.5 s)
     sustained = None
-    if not args.no_sustained and args.config != "C5":
+    if args.full and not args.no_sustained and args.config != "C5":
         n_sus = max(args.steps, int(np.ceil(args.sustained_seconds * 1e3 / regions[0])))
         dt_s, _ = timed(n_sus, 9)
         sustained = {"steps": n_sus, "seconds": dt_s, "ms_per_step": dt_s / n_sus * 1e3, "value": B * N * n_sus / dt_s,
@@ -714,6 +771,7 @@ def main():
                    "obs_len": cfg.obs_len, "pred_len": cfg.pred_len, "train_net": cfg.train_net,
                    "parallelism": f"dp{N}", "trainable_floats": sum(p.numel() for p in model.parameters() if p.requires_grad)},
         "final_loss": loss,
+        "full": args.full,
         "timed_regions": {"ms_per_step": [round(r_, 4) for r_ in regions], "median_ms_per_step": float(np.median(regions)),
                           "min_ms_per_step": min(regions), "max_ms_per_step": max(regions),
                           "median_value": B * N / (float(np.median(regions)) * 1e-3),
@@ -747,10 +805,11 @@ def main():
         out["world"]["distinct_devices"] = len(set(uuids))
     else:
         out["world"] = {"world_size": 1, "backend": None, "ranks": [mine], "allreduce_floats_per_step": 0}
-    gf, mb = STEP_WORK[args.config]
-    out["step_roofline"] = step_roofline(value / N, gf, mb, executed_gflop_per_traj)
+    if args.full:
+        gf, mb = STEP_WORK[args.config]
+        out["step_roofline"] = step_roofline(value / N, gf, mb, executed_gflop_per_traj)
 
-    if args.no_roofline:
+    if args.no_roofline or not args.full:
         pass
     elif args.config == "C5":
         if rank == 0:
@@ -856,6 +915,9 @@ def main():
         total_conv_ms = sum(v["ms"] for v in agg.values())
         out["conv_share_of_step"] = total_conv_ms / out["ms_per_step"]
     if dp is not None:
+        out["world"]["allreduce_transport"] = "oneshot (ynet_allreduce_sum, HIP IPC)" if dp._comm is not None else f"torch.distributed ({dist.get_backend()})"
+        out["world"]["transport_note"] = dp.transport_note
+    if args.full and dp is not None:
         # ---- the collective on its own and the split of a replayed step around it (graph A = forward / backward, eager
         # all-reduce of the flat gradient buffer, graph B = optimizer / read-out), HIP events on the step's stream
         sgm = pkg("utils.step_graph")
@@ -873,8 +935,6 @@ def main():
         torch.cuda.synchronize()
         dp.flat = keep
         out["world"]["allreduce_us_per_step"] = ev0.elapsed_time(ev1) * 1e3 / 50
-        out["world"]["allreduce_transport"] = "oneshot (ynet_allreduce_sum, HIP IPC)" if dp._comm is not None else f"torch.distributed ({dist.get_backend()})"
-        out["world"]["transport_note"] = dp.transport_note
         split = None
         for c in sgm._caches.get(model, {}).values():
             for e in c.entries.values():
@@ -882,7 +942,7 @@ def main():
                     split = e.profile_split(10)
         out["world"]["replayed_step_split_ms"] = split      # {"graph_a", "allreduce", "graph_b"} per step, or None (eager / single graph)
         dist.barrier()
-    if rank == 0 and N == 1 and args.config == "C2" and not args.no_c5:
+    if args.full and rank == 0 and N == 1 and args.config == "C2" and not args.no_c5:
         # ---- BASELINE.json's HBM-bound roofline point (configs[4]: K = 20 goal-decoder sweep, B = 128) in the default run:
         # two warm-up batches (the first ones grow the caching allocator's pools: 150 instead of 121 ms per batch) + four timed
         # batches of the evaluation sweep, and its read-out kernel timed in isolation
@@ -907,7 +967,7 @@ def main():
                      "sweep_launch": pkg("utils.evaluate").last_sweep_launch(),
                      "roofline": readout_roofline(ops, ynet, cfg5, B5, H5, W5, dev)}
         del m5
-    if rank == 0 and N == 1 and args.config == "C2" and not args.no_legs:
+    if args.full and rank == 0 and N == 1 and args.config == "C2" and not args.no_legs:
         # ---- the other single-GPU training configs of BASELINE.json, driver-timed: C1 (every weight trains: the filter-gradient
         # kernels and ynet_adam_step over 1.64 M parameters) and C4 (Y-Net-Mod, 512x512, per-GPU batch 16): 3 steps of warm-up
         # (eager, capture + replay, replay), then 5 replayed steps between two synchronisations
@@ -937,7 +997,7 @@ def main():
                                 "ms_per_step": dtl / 5 * 1e3, "step_launch": "hipGraph replay" if captured else "eager",
                                 "step_roofline": step_roofline(5 * Bl / dtl, gfl, mbl, fcl.flops / Bl / 1e9)}
             del ml, optl
-    if rank == 0 and N == 1 and not args.no_cpu_baseline and args.config != "C5":
+    if args.full and rank == 0 and N == 1 and not args.no_cpu_baseline and args.config != "C5":
         # ---- the ONLY place the oracle is imported: the CPU baseline and the parity check (oracle = checker)
         from oracle import ynet_oracle as O
         out["cpu_baseline"], first, replay = cpu_baseline(O, oracle_cfg(O, cfg), H, W, args.cpu_batch, big_batch=B)

@@ -8,22 +8,28 @@ bit-identical and the key sets must match, so a user can move checkpoints betwee
 No kernels run: construction, state_dict and torch.save/load only (CPU).
 
     python oracle/check_ckpt_roundtrip.py      # prints one line per case, exits non-zero on a mismatch
+    python oracle/check_ckpt_roundtrip.py --record tests/golden/ckpt_roundtrip.npz
+
+--record also writes what the reference did, per case, as names and SHA-256 digests of tensor bytes (no tensors): the key order
+of its model, what its model held after loading the product's checkpoints, and what its own full / delta checkpoints held.
+tests/test_host_logic.py checks the product against that file without the reference.
 """
 import contextlib
+import hashlib
 import importlib
 import io
 import os
 import sys
 import tempfile
 
+import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 REF = "/root/reference"
-sys.path[:0] = [os.path.join(HERE, "_stubs"), REF, ROOT]
-
-from models.trainer import YNetTrainer as RefTrainer                     # noqa: E402  (reference)
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
 
 from oracle import ynet_oracle as O                                      # noqa: E402
 
@@ -44,6 +50,12 @@ def quiet(fn, *a, **k):
         return fn(*a, **k)
 
 
+def digest(t):
+    """SHA-256 of a tensor's dtype, shape and bytes (the bit-identity the round trip asserts)."""
+    t = t.detach().cpu().contiguous()
+    return hashlib.sha256(f"{t.dtype} {tuple(t.shape)} ".encode() + t.view(torch.uint8).numpy().tobytes()).hexdigest()
+
+
 def same(a, b, what):
     ka, kb = list(a.keys()), list(b.keys())
     assert ka == kb, f"{what}: key sets differ: {sorted(set(ka) ^ set(kb))[:6]}"
@@ -61,10 +73,21 @@ CASES = {
 }
 
 
-def main():
+def main(record=None):
+    sys.path[:0] = [os.path.join(HERE, "_stubs"), REF]
+    from models.trainer import YNetTrainer as RefTrainer                 # (reference)
     cpu = torch.device("cpu")
+    rec = {}
+
+    def put(i, key, names, tensors=None, params=None):
+        rec[f"c{i}/{key}/keys"] = np.array(list(names))
+        if tensors is not None:
+            rec[f"c{i}/{key}/sha256"] = np.array([digest(tensors[k]) for k in names])
+        if params is not None:
+            rec[f"c{i}/{key}/is_param"] = np.array([isinstance(params[k], torch.nn.Parameter) for k in names])
+
     with tempfile.TemporaryDirectory() as tmp:
-        for name, mk in CASES.items():
+        for i, (name, mk) in enumerate(CASES.items()):
             cfg = mk()
             p = params_for(cfg)
             sd = O.make_state_dict(cfg, seed=7, lora_b_std=0.05, adapter_std=0.05)
@@ -78,6 +101,7 @@ def main():
             ref = quiet(RefTrainer, p, device=cpu)
             quiet(ref.load_params, full)
             same(ref.model.state_dict(), prod.model.state_dict(), name + " [product full -> reference]")
+            put(i, "ref_after_product_full", ref.model.state_dict().keys(), ref.model.state_dict())
             if cfg.train_net not in ("train", "all"):
                 ck = torch.load(delta, weights_only=False)
                 trainable = [n for n, q in prod.model.named_parameters() if q.requires_grad]
@@ -86,6 +110,7 @@ def main():
                 ref2 = quiet(RefTrainer, p, device=cpu)
                 quiet(ref2.load_separated_params, base, delta)
                 same(ref2.model.state_dict(), prod.model.state_dict(), name + " [product base + delta -> reference]")
+                put(i, "ref_after_product_delta", ref2.model.state_dict().keys(), ref2.model.state_dict())
             # ---- reference writes, product reads
             for q in ref.model.parameters():
                 q.data.add_(0.01)
@@ -96,6 +121,10 @@ def main():
             ref.save_params(rdelta, cfg.train_net)
             rfull = os.path.join(tmp, "ref_full.pt")
             torch.save(ref.model.state_dict(), rfull)
+            ck = torch.load(rdelta, weights_only=False)
+            put(i, "ref_delta", ck.keys(), ck, ck)
+            put(i, "ref_full", ref.model.state_dict().keys(), ref.model.state_dict())
+            put(i, "ref_params", [n for n, _ in ref.model.named_parameters()])
             prod2 = quiet(trn.YNetTrainer, p, device=cpu)
             quiet(prod2.load_params, rfull)
             same(prod2.model.state_dict(), ref.model.state_dict(), name + " [reference full -> product]")
@@ -107,7 +136,11 @@ def main():
                 assert torch.equal(got[k], want[k]), f"{name} [reference delta -> product]: {k}"
             print(f"ok  {name}: {len(sd)} tensors, delta {os.path.getsize(delta)} B, full {os.path.getsize(full)} B")
     print("checkpoint round trip: all cases identical in both directions")
+    if record:
+        rec["cases"] = np.array(list(CASES))
+        np.savez_compressed(record, **rec)
+        print(f"recorded {record}")
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[sys.argv.index("--record") + 1] if "--record" in sys.argv else None)

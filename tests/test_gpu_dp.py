@@ -97,6 +97,30 @@ def test_bench_launcher_reports_a_failing_rank(dev):
     assert "rank 1 fails on purpose" in tail and "a rank failed" in tail, tail[-1500:]
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_outputs(dev, tmp_path):
+    """A plain `bench.py --gpus 1` run: the line's contract fields, --steps timed steps on the replayed graph, none of the --full
+    figures; --dump-outputs writes the timed call's loss / ADE / FDE and the trainable tensors with their last gradients."""
+    import json
+    import numpy as np
+    out = tmp_path / "dump"
+    rc, tail = launch([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
+                       "--dump-outputs", str(out)], timeout=600)
+    assert rc == 0, tail[-3000:]
+    d = json.loads([ln[ln.index('{"metric"'):] for ln in tail.splitlines() if '{"metric"' in ln][-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False and d["step_launch"] == "hipGraph replay"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 4 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert k in d
+    assert not {"cpu_baseline", "parity_check", "roofline", "step_roofline", "sustained", "c5", "c1", "c4"} & set(d)
+    assert float(np.load(out / "loss.npy")[0]) == d["final_loss"]
+    params = sorted(p.name for p in out.glob("param.*.npy"))
+    assert params and sorted(p.name for p in out.glob("grad.*.npy")) == ["grad." + n[len("param."):] for n in params]
+    for f in out.glob("*.npy"):
+        a = np.load(f)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), f.name
+    assert sum(int(np.load(f).size) for f in out.glob("param.*.npy")) == d["config"]["trainable_floats"]
+
+
 @pytest.mark.parametrize("collective", ["rccl", "oneshot"])
 def test_bench_multi_rank_line_reports_the_collective_and_the_step_graphs(dev, collective):
     """`python bench.py --gpus 2` on the development path (one device, gloo control plane) prints the fields the
@@ -110,7 +134,7 @@ def test_bench_multi_rank_line_reports_the_collective_and_the_step_graphs(dev, c
     if n_gpu < 2:
         env.update(YNET_DIST_BACKEND="gloo", YNET_BENCH_SINGLE_DEVICE="1")
     rc, tail = launch([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "3", "--batch", "4",
-                       "--no-cpu-baseline", "--no-roofline", "--no-repeats", "--no-sustained"], env=env, timeout=900)
+                       "--full", "--no-cpu-baseline", "--no-roofline", "--no-repeats", "--no-sustained"], env=env, timeout=900)
     assert rc == 0, tail[-3000:]
     lines = [ln[ln.index('{"metric"'):] for ln in tail.splitlines() if '{"metric"' in ln]
     assert lines, tail[-2000:]

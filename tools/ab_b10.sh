@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cd "$R"
 run() {  # label, batch, env...
   local label=$1 b=$2; shift 2
-  env "$@" python bench.py --batch $b --steps 40 --no-cpu-baseline --no-c5 --no-legs --no-sustained --no-roofline 2>/dev/null | python -c "
+  env "$@" python bench.py --full --batch $b --steps 40 --no-cpu-baseline --no-c5 --no-legs --no-sustained --no-roofline 2>/dev/null | python -c "
 import json,sys
 d=json.load(sys.stdin); print('$label', 'B$b', [round(x,4) for x in d['timed_regions']['ms_per_step']])"
 }

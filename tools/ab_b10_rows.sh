@@ -1,5 +1,6 @@
-mkdir -p gpurun_out/b10r
-run() { tag=$1; shift; env "$@" python bench.py --batch 10 --steps 100 > gpurun_out/b10r/$tag.json 2>gpurun_out/b10r/$tag.err; }
+OUT=${1:?usage: bash tools/ab_b10_rows.sh OUTDIR}
+mkdir -p "$OUT"
+run() { tag=$1; shift; env "$@" python bench.py --full --batch 10 --steps 100 > "$OUT/$tag.json" 2> "$OUT/$tag.err"; }
 run base A=1
 run r1dma YNET_CONV_DMA_R1=1
 run r2min128 YNET_CONV_R2_MIN=128

@@ -5,7 +5,7 @@ cd $R
 for rep in 1 2 3; do
 for v in 0 1; do
   for c in ${AB_CONFIGS:-C2}; do
-    YNET_CONV_PRED_BCE=$v python3 bench.py --config $c --steps 30 --warmup 10 --no-cpu-baseline --no-roofline --no-c5 --no-legs --sustained-seconds 3 2>/dev/null | python3 -c "
+    YNET_CONV_PRED_BCE=$v python3 bench.py --full --config $c --steps 30 --warmup 10 --no-cpu-baseline --no-roofline --no-c5 --no-legs --sustained-seconds 3 2>/dev/null | python3 -c "
 import sys,json
 for ln in sys.stdin:
     if ln.startswith('{\"metric\"'):

@@ -3,7 +3,7 @@
 #   gpurun -- 'bash tools/ab_knobs.sh "X=0" "YNET_CONV_X4=0" ...'
 run() {
   for rep in 1 2; do
-    env "$@" python bench.py --no-cpu-baseline --steps 12 --warmup 3 --layers 2>/tmp/layers.txt | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('   ms/step', round(d['ms_per_step'],3), end='')"
+    env "$@" python bench.py --full --no-cpu-baseline --steps 12 --warmup 3 --layers 2>/tmp/layers.txt | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('   ms/step', round(d['ms_per_step'],3), end='')"
     awk '/LAYER/ {s+=$(NF-3)} END {print "   conv us/step", s}' /tmp/layers.txt
   done
 }

@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 for lib in "$@"; do
   rm -rf /tmp/abt; 
-  YNET_HIP_LIB=$([ "$lib" = current ] && echo "" || echo $R/$lib) YNET_SERIAL_DECODERS=1 timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/abt -o t -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-roofline > /tmp/abt.log 2>&1
+  YNET_HIP_LIB=$([ "$lib" = current ] && echo "" || echo $R/$lib) YNET_SERIAL_DECODERS=1 timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/abt -o t -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-roofline > /tmp/abt.log 2>&1
   python3 - "$lib" <<'PY'
 import glob, sqlite3, sys
 db = glob.glob("/tmp/abt/**/*results.db", recursive=True)[0]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-LAUNCH-SHAPE roofline table of one C2 step: joins the launch order bench.py records for one eager serial
-step (`bench.py --conv-layers FILE`: kernel instantiation, (B, H, W, cin, cout, K), HIP-event microseconds, direct-form GFLOP,
+step (`bench.py --full --conv-layers FILE`: kernel instantiation, (B, H, W, cin, cout, K), HIP-event microseconds, direct-form GFLOP,
 algorithmic bytes) with rocprofv3's kernel-only durations of the same eager serial run (--kernel-trace, YNET_STEP_GRAPH=0
 YNET_SERIAL_DECODERS=1) and, when present, with the FETCH_SIZE / WRITE_SIZE counter passes -- all three list the convolution
 launches of a step in the same order, which the kernel names verify row by row.

@@ -4,7 +4,7 @@ sys.path.insert(0, os.getcwd())
 os.environ["YNET_STEP_GRAPH"] = "0"
 import torch
 from torch.profiler import profile, ProfilerActivity
-sys.argv = ["bench.py", "--config", sys.argv[1] if len(sys.argv) > 1 else "C1", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-c5", "--no-roofline", "--no-repeats"]
+sys.argv = ["bench.py", "--full", "--config", sys.argv[1] if len(sys.argv) > 1 else "C1", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-c5", "--no-roofline", "--no-repeats"]
 import runpy
 with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA], record_shapes=True, with_stack=True) as prof:
     try:

@@ -10,7 +10,7 @@ i=0
 for grp in "SQ_BUSY_CU_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_WAIT_ANY" \
            "SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VMEM_RD SQ_VMEM_TA_ADDR_FIFO_FULL"; do
   i=$((i+1))
-  timeout 400 rocprofv3 --pmc $grp -d "$OUT/p$i" -o c5 -- python3 "$R/bench.py" --config C5 --steps 1 --warmup 1 --no-cpu-baseline --no-roofline > "$OUT/p$i.log" 2>&1
+  timeout 400 rocprofv3 --pmc $grp -d "$OUT/p$i" -o c5 -- python3 "$R/bench.py" --full --config C5 --steps 1 --warmup 1 --no-cpu-baseline --no-roofline > "$OUT/p$i.log" 2>&1
   echo "pass $i rc=$?"
 done
 python3 - "$OUT" <<'PY'

@@ -14,7 +14,7 @@ def spy2(x, weight, bias, relu, cache, lora_a=None, lora_b=None, scale=1.0, pool
     if pool: cnt["pool_req"] += 1
     return c2(x, weight, bias, relu, cache, lora_a, lora_b, scale, pool)
 ops.conv2d = spy2
-sys.argv = ["bench.py", "--config", sys.argv[1], "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-c5", "--no-roofline", "--no-repeats"]
+sys.argv = ["bench.py", "--full", "--config", sys.argv[1], "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-c5", "--no-roofline", "--no-repeats"]
 os.environ["YNET_STEP_GRAPH"] = "0"
 import runpy
 try: runpy.run_path("bench.py", run_name="__main__")

@@ -12,7 +12,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/prof_c5_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --config C5 --no-cpu-baseline --no-roofline"
+B="python3 $R/bench.py --full --config C5 --no-cpu-baseline --no-roofline"
 export YNET_SERIAL_DECODERS=1
 rm -rf /tmp/tr_c5
 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/tr_c5 -o t -- $B --steps 3 --warmup 2 > "$OUT/trace_c5_serial.log" 2>&1

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/prof_$CFG
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run -- python3 "$R/bench.py" --config "$CFG" --steps "$STEPS" --warmup "$WARM" --no-cpu-baseline --no-roofline > "$OUT/trace.log" 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run -- python3 "$R/bench.py" --full --config "$CFG" --steps "$STEPS" --warmup "$WARM" --no-cpu-baseline --no-roofline > "$OUT/trace.log" 2>&1
 echo "trace rc=$?"
 python3 - "$OUT" <<'PY'
 import glob, sqlite3, sys, os

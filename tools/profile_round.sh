@@ -15,7 +15,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 rm -rf /tmp/tr_*
 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/tr_graph -o t -- $B --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-c5 --no-legs --no-sustained --no-repeats > "$OUT/trace_graph.log" 2>&1
 echo "trace graph rc=$?"; python3 "$R/tools/trace_summary.py" /tmp/tr_graph "$OUT/${TAG}_bench_C2" --tail-frac 0.6 > "$OUT/timeline_graph.txt"

@@ -10,7 +10,7 @@ OUT=$R/gpurun_out/rccl_$TAG
 mkdir -p "$OUT"
 cd "$R"
 python3 -m pytest tests/test_gpu_dp.py -q -x -k forced_single_rank > "$OUT/pytest.log" 2>&1; echo "pytest rc=$?"; tail -5 "$OUT/pytest.log"
-B="python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-c5 --no-legs --no-sustained"
+B="python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-c5 --no-legs --no-sustained"
 $B > "$OUT/${TAG}_bench_C2_plain_line.json" 2> "$OUT/plain.err"; echo "plain rc=$?"
 YNET_DP_FORCE=1 $B > "$OUT/${TAG}_bench_C2_forced_rccl_line.json" 2> "$OUT/forced.err"; echo "forced rccl rc=$?"
 YNET_DP_FORCE=1 YNET_ALLREDUCE=oneshot $B > "$OUT/${TAG}_bench_C2_forced_oneshot_line.json" 2> "$OUT/forced1.err"; echo "forced oneshot rc=$?"

@@ -10,7 +10,7 @@ def timed(self, batch, scene_image):
     times.append((time.perf_counter() - t0, str(batch.dtype), batch.is_cuda, batch.is_contiguous(), tuple(batch.shape)))
     return r
 sg.CapturedStep.replay = timed
-sys.argv = ["bench.py", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-c5", "--no-roofline", "--no-repeats"]
+sys.argv = ["bench.py", "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-c5", "--no-roofline", "--no-repeats"]
 import runpy
 try:
     runpy.run_path("bench.py", run_name="__main__")
