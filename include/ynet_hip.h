@@ -242,7 +242,8 @@ int ynet_upsample2x_conv2d_winograd(const float* src, long long src_bs, const fl
  *                version, or a plan that differs: another batch / raster size can choose another family); a cache belongs to ONE
  *                (layer, direction) and one stream order -- a caller that shares it between streams orders them itself (taken->transformed
  *                tells when a transform was enqueued).
- *   flags        YNET_AUTO_* below: development switches that restrict the choice (results then differ by fp32 rounding only).
+ *   flags        YNET_AUTO_* below: development switches that restrict the choice (results then differ by fp32 rounding only); YNET_AUTO_UPCONV_BWD
+ *                selects another operation instead (an up-convolution's data gradient at the low resolution, see ynet_upconv_dgrad_ring).
  *   taken        (optional) what ran: the family, the launches with the template arguments their rocprofv3 kernel names carry, whether
  *                the optional outputs wbits_out / pool_code were WRITTEN (they are only when the launch taken is the Winograd one they
  *                belong to; a caller keeps them only then).
@@ -254,6 +255,7 @@ int ynet_upsample2x_conv2d_winograd(const float* src, long long src_bs, const fl
 #define YNET_AUTO_NO_POOL_CODE 8u       /* pool_code is never written */
 #define YNET_AUTO_NO_RELU_WBITS 16u     /* wbits_out is never written, relu_wbits never read (relu_of's float activation instead) */
 #define YNET_AUTO_NO_SPLIT48 32u        /* a [16, 32]-channel data gradient as two launches, not ynet_conv2d_winograd_split */
+#define YNET_AUTO_UPCONV_BWD 64u        /* a FORM, not a restriction: the data gradient of an up-convolution at the low resolution, see ynet_upconv_dgrad_ring below */
 typedef struct YnetConvAuto {
     const float* src[4];
     int src_c[4];
@@ -315,14 +317,26 @@ int ynet_conv2d_auto_plan(const YnetConvAuto* desc, YnetConvTaken* taken);
  * VERDICT r5 item 3).  Up^T . conv^T is itself a 3 x 3 convolution at the LOW resolution over the space-to-depth output gradient D [4 cout][h][w]: output pixel
  * (2 i + py, 2 j + px) of the forward pass sees the 3 x 3 low-resolution patch around (i, j) through the effective filter
  *     Keff[(py, px, co)][ci][a][b] = sum_{ty, tx} M_py[a][ty] K[co][ci][ty][tx] M_px[b][tx],   M_0 = [[.75 .25 0] [.25 .75 .75] [0 0 .25]],  M_1 = [[.25 0 0] [.75 .75 .25] [0 .25 .75]]
- * so dx = the ordinary data gradient of a convolution with weight Keff [4 cout][cin][3][3] applied to D -- one ynet_conv2d_auto call (mode-1 packed Keff, relu_of = x) --
- * EXCEPT on the outermost ring of dx: there the bilinear clamp (L[-1] = L[0]) and the zero padding of the UP-SAMPLED image differ from that formula.  The difference is again
- * linear and thin: ynet_upconv_dgrad_ring adds it to the ring pixels of dx (masked by relu_of > 0 when given):
+ * so dx = the ordinary data gradient of a convolution with weight Keff [4 cout][cin][3][3] applied to D, EXCEPT on the outermost ring of dx: there the bilinear
+ * clamp (L[-1] = L[0]) and the zero padding of the UP-SAMPLED image differ from that formula.  The difference is again linear and thin (ynet_upconv_dgrad_ring):
  *     rows 0 / h-1:  sum_{c', b} tables[s * 3 + b][c'][ci] D[c'][row][j - b + 1],  tables[s*3+b] = sum dM_s[py][ty] K M_px[b][tx]
  *     columns 0 / w-1:  tables[6 + s * 3 + a] alike;  the four corners additionally tables[12 + 2 sv + sh][c'][ci] D[c'][corner]
  *     dM_0 = .25 [[-1 1 0] [1 0 0]] (couples to L[0]),  dM_1 = .25 [[0 0 1] [0 1 -1]] (couples to L[h-1])
- * (motion-style-transfer_amd/ops.py::upconv_s2d_tables builds Keff and the 16 tables from the layer's filter; tests compare with autograd in fp64.)
+ *
+ * ONE CALL (what the package runs): ynet_conv2d_auto with flags | YNET_AUTO_UPCONV_BWD -- src[0] = D (src_c[0] = 4 cout), dst[0] = dx (dst_c[0] = cin), wp = the
+ * layer's RAW filter K [cout][cin][3][3] (not packed), H x W = h x w (the low resolution), K = 3, relu_of optional (dx is then written through that activation's
+ * ReLU backward: relu_of > 0 ? dx : 0, ring included), nothing else (no bias, relu, mask, upsample2x, pooled, addend, bit masks, dst_s2d: refused).  The cache
+ * (ynet_conv2d_auto_cache_floats of the same descriptor) receives Keff, the 16 tables and the transforms of Keff the plan takes, all made when cache_tag /
+ * wp_version do not match (taken->transformed); give this form a cache of its own (one layer, one plan).  taken: the low-resolution data gradient's family /
+ * variant, nlaunch with the ring launch counted; ynet_conv2d_auto_plan answers the same without launching.
+ *
+ * THE PIECES: ynet_upconv_tables writes, from K, Keff in the layout of ynet_pack_weight(Keff, 4 cout, cin, 3, mode 1) ([rows][9][cols], rows = 4 cout padded to
+ * 16 + 16, cols = cin padded to 64; the padding zeroed) and the tables [16][4 cout][cin], every entry summed in fp64 without contraction and rounded to fp32 once;
+ * ynet_upconv_tables_floats gives both sizes (either pointer may be NULL; -1 for a bad shape).  The data gradient is then one ynet_conv2d_auto call (packed Keff,
+ * relu_of = x) and ynet_upconv_dgrad_ring adds the ring to dx (masked by relu_of > 0 when given).
  * D: [B][C4 = 4 cout][h][w] (batch stride d_bs); tables: [16][C4][cin] floats; dx [B][cin][h][w] is updated in place. */
+long long ynet_upconv_tables_floats(int cout, int cin, long long* keff_floats, long long* table_floats);
+int ynet_upconv_tables(const float* w, int cout, int cin, float* keff_packed, float* tables, void* stream);
 int ynet_upconv_dgrad_ring(const float* D, long long d_bs, const float* tables, const float* relu_of, long long relu_of_bs, float* dx, long long dx_bs,
                            int B, int C4, int cin, int h, int w, void* stream);
 

@@ -39,6 +39,7 @@ class ConvTaken(ctypes.Structure):
 
 
 AUTO_NO_WINOGRAD, AUTO_NO_WINOGRAD16, AUTO_WINOGRAD16_FOR_16, AUTO_NO_POOL_CODE, AUTO_NO_RELU_WBITS, AUTO_NO_SPLIT48 = 1, 2, 4, 8, 16, 32
+AUTO_UPCONV_BWD = 64      # the form of ynet_conv2d_auto that runs an up-convolution's data gradient at the low resolution (wp = the raw filter)
 
 # name -> (restype, argtypes); must list every function of include/ynet_hip.h
 SIGNATURES = {
@@ -67,6 +68,8 @@ SIGNATURES = {
     "ynet_conv2d_winograd_split_supported": (c_i, [c_i, c_i, c_i, c_i]),
     "ynet_conv2d_winograd_split": (c_i, [c_fp, c_ll, c_fp, c_fp, c_ll, c_i, c_fp, c_ll, c_i, c_i, c_i, c_i, c_fp]),
     "ynet_upconv_dgrad_ring": (c_i, [c_fp, c_ll, c_fp, c_fp, c_ll, c_fp, c_ll, c_i, c_i, c_i, c_i, c_i, c_fp]),
+    "ynet_upconv_tables_floats": (c_ll, [c_i, c_i, PLL, PLL]),
+    "ynet_upconv_tables": (c_i, [c_fp, c_i, c_i, c_fp, c_fp, c_fp]),
     "ynet_conv2d_winograd_dgrad_relu": (c_i, [c_fp, c_ll, c_fp, c_fp, c_ll, c_fp, c_ll, c_i, c_i, c_i, c_i, c_i, c_fp]),
     "ynet_conv2d_winograd_cat_supported": (c_i, [c_i, c_i, c_i, PI, c_i, c_i, c_i]),
     "ynet_winograd_filter_cat_floats": (c_ll, [PI, c_i, c_i]),

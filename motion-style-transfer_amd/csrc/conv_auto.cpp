@@ -332,11 +332,29 @@ int transform(const YnetConvAuto* a, const Plan& p, void* stream) {
     return 0;
 }
 
+// ---- YNET_AUTO_UPCONV_BWD: the data gradient of an up-convolution (bilinear x2 + 3 x 3 conv, models/ynet.py:463-464) at the LOW resolution ----------------------
+// The cache holds [Keff, mode-1 packed | the 16 ring tables | the transforms the low-resolution plan takes of Keff]; Keff and the tables are made from the RAW filter
+// (ynet_upconv_tables) and the transforms from Keff, all under the one tag.  Then: the plan's data gradient of Keff over the space-to-depth gradient, then the ring.
+struct UpPlan {
+    YnetConvAuto in;           // the low-resolution data gradient of Keff (wp, cache: inside the caller's cache)
+    Plan p;
+    int cout, cin;
+    long long tab_off, wino_off, cache_floats;
+};
+
+int make_up_plan(const YnetConvAuto* a, UpPlan& u);
+int run_upconv_bwd(const YnetConvAuto* a, YnetConvTaken* taken, void* stream);
+int run_plan(const YnetConvAuto* a, const Plan& p, YnetConvTaken t, YnetConvTaken* taken, void* stream);
+
 }  // namespace
 
 extern "C" {
 
 long long ynet_conv2d_auto_cache_floats(const YnetConvAuto* a) {
+    if (a && (a->flags & YNET_AUTO_UPCONV_BWD)) {
+        UpPlan u;
+        return make_up_plan(a, u) ? -1 : u.cache_floats;
+    }
     Plan p;
     if (!a || make_plan(a, p)) return -1;
     return p.cache_floats;
@@ -352,6 +370,16 @@ long long ynet_conv2d_auto_workspace_floats(const YnetConvAuto* a) {
 
 int ynet_conv2d_auto_plan(const YnetConvAuto* a, YnetConvTaken* taken) {
     YNET_REQUIRE(a != nullptr && taken != nullptr, "conv2d_auto_plan: null pointer");
+    if (a->flags & YNET_AUTO_UPCONV_BWD) {
+        UpPlan u;
+        if (int rc = make_up_plan(a, u)) return rc;
+        const Plan& p = u.p;
+        memset(taken, 0, sizeof(*taken));
+        taken->family = p.family;
+        taken->variant = p.variant;
+        taken->nlaunch = (p.family ? (p.variant == 23 ? 1 : (p.npieces > 0 ? p.npieces : (p.nl > 0 ? p.nl : 1))) : 1) + 1;      // (+ the ring)
+        return 0;
+    }
     YNET_REQUIRE(a->nsrc >= 1 && a->nsrc <= 4 && a->ndst >= 1 && a->ndst <= 4, "conv2d_auto_plan: 1..4 sources and destinations are required");
     Plan p;
     if (int rc = make_plan(a, p)) return rc;
@@ -364,6 +392,7 @@ int ynet_conv2d_auto_plan(const YnetConvAuto* a, YnetConvTaken* taken) {
 
 int ynet_conv2d_auto(const YnetConvAuto* a, YnetConvTaken* taken, void* stream) {
     YNET_REQUIRE(a != nullptr, "conv2d_auto: null descriptor");
+    if (a->flags & YNET_AUTO_UPCONV_BWD) return run_upconv_bwd(a, taken, stream);
     YNET_REQUIRE(a->nsrc >= 1 && a->nsrc <= 4 && a->ndst >= 1 && a->ndst <= 4 && a->wp, "conv2d_auto: 1..4 sources, 1..4 destinations and a packed filter are required");
     YNET_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0 && (a->K == 1 || a->K == 3 || a->K == 5), "conv2d_auto: bad shape B %d %dx%d K %d", a->B, a->H, a->W, a->K);
     Plan p;
@@ -384,6 +413,15 @@ int ynet_conv2d_auto(const YnetConvAuto* a, YnetConvTaken* taken, void* stream) 
             t.transformed = 1;
         }
     }
+    return run_plan(a, p, t, taken, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+// the launches of a plan whose filters are in the cache (t: family, variant and `transformed` already set)
+int run_plan(const YnetConvAuto* a, const Plan& p, YnetConvTaken t, YnetConvTaken* taken, void* stream) {
     const int B = a->B, H = a->H, W = a->W, K = a->K, relu = a->relu ? 1 : 0;
     int ctot = 0;
     for (int i = 0; i < a->ndst; ++i) ctot += a->dst_c[i];
@@ -542,4 +580,69 @@ int ynet_conv2d_auto(const YnetConvAuto* a, YnetConvTaken* taken, void* stream) 
     }
 }
 
-}  // extern "C"
+int make_up_plan(const YnetConvAuto* a, UpPlan& u) {
+    YNET_REQUIRE(a->nsrc == 1 && a->ndst == 1, "conv2d_auto (upconv_bwd): one source (the space-to-depth output gradient) and one destination (dx), not %d and %d", a->nsrc, a->ndst);
+    YNET_REQUIRE(!a->upsample2x && !a->pooled && !a->pool_code && !a->addend && !a->mask && !a->bias && !a->relu && !a->bits_out && !a->relu_bits && !a->wbits_out &&
+                 !a->relu_wbits && !a->dst_s2d[0] && a->src_bmod[0] <= 0,
+                 "conv2d_auto (upconv_bwd): relu_of is the only optional operand (no upsample2x, pooled, pool_code, addend, mask, bias, relu, bit masks, dst_s2d, batch modulus)");
+    YNET_REQUIRE(a->K == 3 && a->src_c[0] >= 4 && (a->src_c[0] & 3) == 0 && a->dst_c[0] >= 1, "conv2d_auto (upconv_bwd): K 3, src_c[0] = 4 cout, dst_c[0] = cin (K %d, src_c %d, dst_c %d)",
+                 a->K, a->src_c[0], a->dst_c[0]);
+    YNET_REQUIRE(a->B > 0 && a->H >= 2 && a->W >= 2, "conv2d_auto (upconv_bwd): the low-resolution map must be at least 2 x 2 (B %d, %dx%d)", a->B, a->H, a->W);
+    const int c4 = a->src_c[0], cin = a->dst_c[0];
+    const long long hw = (long long)a->H * a->W;
+    YNET_REQUIRE(a->src_bs[0] >= c4 * hw && a->dst_bs[0] >= cin * hw && (!a->relu_of || a->relu_of_bs >= cin * hw), "conv2d_auto (upconv_bwd): batch strides smaller than the images");
+    // (ynet_upconv_dgrad_ring keeps three tables and a D tile of 66 pixels per channel in 64 KB of LDS)
+    YNET_REQUIRE((3ll * c4 * cin + c4 * 66ll + 256) * 4 <= 64 * 1024, "conv2d_auto (upconv_bwd): 4 cout %d x cin %d ring tables do not fit the ring kernel's LDS", c4, cin);
+    memset(&u, 0, sizeof(u));
+    u.cout = c4 / 4;
+    u.cin = cin;
+    long long kf = 0, tf = 0;
+    YNET_REQUIRE(ynet_upconv_tables_floats(u.cout, cin, &kf, &tf) > 0, "conv2d_auto (upconv_bwd): bad shape cout %d cin %d", u.cout, cin);
+    u.tab_off = (kf + 3) & ~3ll;
+    u.wino_off = u.tab_off + ((tf + 3) & ~3ll);
+    u.in = *a;
+    u.in.flags &= ~YNET_AUTO_UPCONV_BWD;
+    u.in.wp = a->cache;
+    u.in.cache = a->cache ? a->cache + u.wino_off : nullptr;
+    u.in.cache_floats = a->cache_floats - u.wino_off;
+    u.in.cache_tag = nullptr;
+    if (int rc = make_plan(&u.in, u.p)) return rc;
+    u.cache_floats = u.wino_off + u.p.cache_floats;
+    return 0;
+}
+
+int run_upconv_bwd(const YnetConvAuto* a, YnetConvTaken* taken, void* stream) {
+    UpPlan u;
+    if (int rc = make_up_plan(a, u)) return rc;
+    YNET_REQUIRE(a->wp && a->src[0] && a->dst[0], "conv2d_auto (upconv_bwd): the raw filter [cout][cin][3][3], the source and the destination are required");
+    YNET_REQUIRE(a->cache && a->cache_tag && a->cache_floats >= u.cache_floats && al(a->cache, 16),
+                 "conv2d_auto (upconv_bwd): this call keeps %lld floats of effective filter, ring tables and transforms (ynet_conv2d_auto_cache_floats): pass a 16-byte aligned cache "
+                 "of that size and its tag", u.cache_floats);
+    YnetConvTaken t;
+    memset(&t, 0, sizeof(t));
+    t.family = u.p.family;
+    t.variant = u.p.variant;
+    unsigned long long sig = signature(u.p);
+    for (long long v : {0x7570636f6e76ll, (long long)u.cout, (long long)u.cin}) {
+        sig ^= (unsigned long long)v;
+        sig *= 1099511628211ull;
+    }
+    sig = sig ? sig : 1;
+    if (a->cache_tag[0] != sig || a->cache_tag[1] != a->wp_version) {
+        if (int rc = ynet_upconv_tables(a->wp, u.cout, u.cin, a->cache, a->cache + u.tab_off, stream)) return rc;
+        if (int rc = transform(&u.in, u.p, stream)) return rc;
+        a->cache_tag[0] = sig;
+        a->cache_tag[1] = a->wp_version;
+        t.transformed = 1;
+    }
+    YnetConvTaken ti;
+    if (int rc = run_plan(&u.in, u.p, t, &ti, stream)) return rc;
+    if (int rc = ynet_upconv_dgrad_ring(a->src[0], a->src_bs[0], a->cache + u.tab_off, a->relu_of, a->relu_of_bs, a->dst[0], a->dst_bs[0], a->B, 4 * u.cout, u.cin, a->H, a->W,
+                                        stream))
+        return rc;
+    ti.nlaunch += 1;      // (the ring)
+    if (taken) *taken = ti;
+    return 0;
+}
+
+}  // namespace

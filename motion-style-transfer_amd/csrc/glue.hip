@@ -1506,9 +1506,10 @@ __global__ __launch_bounds__(256) void upconv_ring_kernel(const float* __restric
         const float* tcol = tab + (long long)(6 + corner * 3) * tstride;
         const float* tx = tab + (long long)(12 + side * 2 + corner) * tstride;
         const int nterm = 4 * C4;                          // (tap 0..2 of the column term, 3 = the corner term) x c'
-        for (int ci = tid & 31; ci < cin; ci += 32) {
+        for (int ci0 = 0; ci0 < cin; ci0 += 32) {          // (a uniform trip count: the loop body holds barriers)
+            const int ci = ci0 + (tid & 31);
             float part = 0.f;
-            for (int k = tid >> 5; k < nterm; k += 8) {
+            for (int k = tid >> 5; k < nterm && ci < cin; k += 8) {
                 const int t = k / C4, c = k - t * C4;
                 float d = 0.f;
                 if (t < 3) {
@@ -1522,7 +1523,7 @@ __global__ __launch_bounds__(256) void upconv_ring_kernel(const float* __restric
             __syncthreads();
             red[(tid >> 5) * 32 + (tid & 31)] = part;
             __syncthreads();
-            if (tid < 32) {
+            if (tid < 32 && ci < cin) {
                 float sum = 0.f;
                 for (int k = 0; k < 8; ++k) sum += red[k * 32 + tid];
                 const long long o = (long long)ci * hw + (long long)fixed * w + jc;

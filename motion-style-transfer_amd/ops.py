@@ -537,6 +537,22 @@ def _auto_tag(tk):
     return "winograd_up:%d" % tk.family
 
 
+def _auto_flags(wino):
+    """The YNET_AUTO_* development switches of a ynet_conv2d_auto call (wino None: implicit GEMM only)."""
+    flags = 0
+    if wino is None or not _wino_allowed:
+        flags |= L.AUTO_NO_WINOGRAD
+    if not _wino16_allowed:
+        flags |= L.AUTO_NO_WINOGRAD16
+    if _wino16_for_16:
+        flags |= L.AUTO_WINOGRAD16_FOR_16
+    if not _pool_code_allowed:
+        flags |= L.AUTO_NO_POOL_CODE
+    if not _split48_allowed:
+        flags |= L.AUTO_NO_SPLIT48
+    return flags
+
+
 def conv2d_auto_raw(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=None, pooled=None, bits_out=None, relu_bits=None, wino=None, wbits_out=None,
                     relu_wbits=None, pool_code=None, addend=None, upsample2x=False, wp_version=1, dst_s2d=None):
     """ONE call of ynet_conv2d_auto (include/ynet_hip.h): the library chooses the kernel family, splits wide layers and keeps the transformed
@@ -569,18 +585,7 @@ def conv2d_auto_raw(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=None, 
         d.wbits_out = wbits_out.data_ptr()
     if relu_wbits is not None:
         d.relu_wbits = relu_wbits.data_ptr()
-    flags = 0
-    if wino is None or not _wino_allowed:
-        flags |= L.AUTO_NO_WINOGRAD
-    if not _wino16_allowed:
-        flags |= L.AUTO_NO_WINOGRAD16
-    if _wino16_for_16:
-        flags |= L.AUTO_WINOGRAD16_FOR_16
-    if not _pool_code_allowed:
-        flags |= L.AUTO_NO_POOL_CODE
-    if not _split48_allowed:
-        flags |= L.AUTO_NO_SPLIT48
-    d.flags = flags
+    d.flags = flags = _auto_flags(wino)
     ent = None
     if wino is not None and not (flags & L.AUTO_NO_WINOGRAD):
         cache, what = wino
@@ -1696,6 +1701,73 @@ def upconv_s2d_tables(weight, cache):
     return ent[1], ent[2], ent[3]
 
 
+def upconv_dgrad_raw(D, weight, dx, relu_of, B, cout, cin, h, w, cache):
+    """dx [B, cin, h, w] = the data gradient of conv3x3(upsample2x(x), weight) from its output gradient written space-to-depth, D [B, 4 cout, h, w] (pointers; relu_of:
+    the pointer of x when dx goes through x's ReLU backward, or None) -- ONE ynet_conv2d_auto call in the YNET_AUTO_UPCONV_BWD form: the library makes the effective
+    filter and the ring tables from the raw filter (ynet_upconv_tables; upconv_s2d_tables is their Python twin) into a buffer of this layer's cache that belongs to
+    this form and this plan alone, then runs the low-resolution data gradient and the ring.  Returns the YnetConvTaken."""
+    lib = _lib()
+    wino = (cache, "dgrad")
+    if not torch.is_grad_enabled() and (h * w < _wino_eval_min_hw or not (_wino_plain_eval if 4 * cout in (16, 32) else _wino_cat_eval)):
+        wino = None      # (the gates conv2d_raw applies to the same data gradient)
+    hw = h * w
+    d = L.ConvAuto()
+    d.nsrc = d.ndst = 1
+    d.src[0], d.src_c[0], d.src_bs[0] = D, 4 * cout, 4 * cout * hw
+    d.dst[0], d.dst_c[0], d.dst_bs[0] = dx, cin, cin * hw
+    if relu_of is not None:
+        d.relu_of, d.relu_of_bs = relu_of, cin * hw
+    d.wp = weight.data_ptr()
+    d.B, d.H, d.W, d.K = B, h, w, 3
+    d.flags = _auto_flags(wino) | L.AUTO_UPCONV_BWD
+    need = lib.ynet_conv2d_auto_cache_floats(ctypes.byref(d))
+    if need <= 0:
+        L.check(1, lib)
+    # one buffer per plan: a captured step keeps reading the buffer of the plan it captured, whatever other batch sizes do eagerly in between
+    key = ("upconv_bwd", B, h, w, relu_of is not None, int(d.flags), int(need))
+    ent = cache.get(key)
+    if ent is None:
+        ent = cache[key] = [torch.empty(need, device=weight.device, dtype=torch.float32), (ctypes.c_ulonglong * 2)(0, 0), None, 0]
+    wkey = (weight.data_ptr(), weight._version)
+    if ent[2] != wkey:      # (a new filter: a new version, the library remakes the tables)
+        ent[2], ent[3] = wkey, ent[3] + 1
+    d.cache, d.cache_floats, d.cache_tag, d.wp_version = ent[0].data_ptr(), ent[0].numel(), ent[1], ent[3]
+    if B * hw <= 65536:                                          # small maps only (see ynet_conv2d_workspace_floats)
+        nws = lib.ynet_conv2d_auto_workspace_floats(ctypes.byref(d))
+        if nws > 0:
+            wkey_ = (weight.device, torch.cuda.current_stream().cuda_stream)
+            ws = _conv_ws.get(wkey_)
+            if ws is None or ws.numel() < nws:
+                ws = _conv_ws[wkey_] = torch.empty(nws, device=weight.device, dtype=torch.float32)
+            d.workspace, d.workspace_floats = ws.data_ptr(), nws
+    tk = L.ConvTaken()
+    L.check(lib.ynet_conv2d_auto(ctypes.byref(d), ctypes.byref(tk), _stream()), lib)
+    if tk.family:
+        wino_stats["launches"] += tk.nlaunch - 1      # (the ring is no Winograd launch)
+        if tk.family in (3, 5):
+            wino_stats["launches16"] = wino_stats.get("launches16", 0) + tk.nlaunch - 1
+    return tk
+
+
+def upconv_tables(weight, cache):
+    """upconv_s2d_tables made by the library (ynet_upconv_tables: one launch, fp64 sums, bit-identical to the einsums): (packed effective filter, ring tables
+    [16][4 cout][cin], a filter cache for the effective filter's transforms), cached per weight version in the layer's cache."""
+    key = ("hip", weight.data_ptr(), weight._version)
+    ent = cache.get("upconv_tables")
+    if ent is None or ent[0] != key:
+        cout, cin = int(weight.shape[0]), int(weight.shape[1])
+        kf, tf = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        lib = _lib()
+        if lib.ynet_upconv_tables_floats(cout, cin, ctypes.byref(kf), ctypes.byref(tf)) < 0:
+            raise ValueError("upconv_tables: bad filter shape %s" % (tuple(weight.shape),))
+        keff = torch.empty(kf.value, device=weight.device, dtype=torch.float32)
+        tables = torch.empty((16, 4 * cout, cin), device=weight.device, dtype=torch.float32)
+        w_ = weight.detach().contiguous()
+        L.check(lib.ynet_upconv_tables(w_.data_ptr(), cout, cin, keff.data_ptr(), tables.data_ptr(), _stream()), lib)
+        ent = cache["upconv_tables"] = (key, keff, tables, {}, w_)
+    return ent[1], ent[2], ent[3]
+
+
 class _UpConvFn(torch.autograd.Function):
     """y = conv3x3(upsample2x(x), W) + b without the up-sampled tensor (models/ynet.py:463-464 as one launch).  The filter is frozen (no
     filter gradient needs the up-sampled input); backward = the convolution's data gradient at the up-sampled size, then the bilinear
@@ -1750,14 +1822,20 @@ class _UpConvFn(torch.autograd.Function):
         if handed:
             # dy's memory holds the gradient space-to-depth, [B, 4 cout, Hl, Wl]: the data gradient of the effective filter at the low resolution (through the ReLU
             # backward of x where that is wanted), then what the bilinear clamp and the up-sampled image's zero padding add on the outermost ring
-            wp_eff, tables, wcache = upconv_s2d_tables(weight, ctx.cache)
             dx = torch.empty((B, cin, Hl, Wl), device=dy.device, dtype=torch.float32)
             masked = bool(ctx.premask and premask and x is not None)
-            conv2d_raw([(dy.data_ptr(), 4 * cout, 4 * cout * Hl * Wl)], None, wp_eff, None, [(dx.data_ptr(), cin, cin * Hl * Wl)], B, Hl, Wl, 3, False,
-                       relu_of=(x.data_ptr(), cin * Hl * Wl) if masked else None, wino=(wcache, "dgrad"))
-            lib = _lib()
-            L.check(lib.ynet_upconv_dgrad_ring(dy.data_ptr(), 4 * cout * Hl * Wl, tables.data_ptr(), x.data_ptr() if masked else None, cin * Hl * Wl, dx.data_ptr(),
-                                               cin * Hl * Wl, B, 4 * cout, cin, Hl, Wl, _stream()), lib)
+            w_ = weight.detach()
+            if not w_.is_contiguous():
+                w_ = ctx.cache["upconv_w"] = w_.contiguous()      # (kept: the library reads it on the stream)
+            if conv_auto:
+                upconv_dgrad_raw(dy.data_ptr(), w_, dx.data_ptr(), x.data_ptr() if masked else None, B, cout, cin, Hl, Wl, ctx.cache)
+            else:      # (YNET_CONV_AUTO=0: the round-5 dispatcher for the data gradient, the tables from the library all the same)
+                wp_eff, tables, wcache = upconv_tables(w_, ctx.cache)
+                conv2d_raw([(dy.data_ptr(), 4 * cout, 4 * cout * Hl * Wl)], None, wp_eff, None, [(dx.data_ptr(), cin, cin * Hl * Wl)], B, Hl, Wl, 3, False,
+                           relu_of=(x.data_ptr(), cin * Hl * Wl) if masked else None, wino=(wcache, "dgrad"))
+                lib = _lib()
+                L.check(lib.ynet_upconv_dgrad_ring(dy.data_ptr(), 4 * cout * Hl * Wl, tables.data_ptr(), x.data_ptr() if masked else None, cin * Hl * Wl, dx.data_ptr(),
+                                                   cin * Hl * Wl, B, 4 * cout, cin, Hl, Wl, _stream()), lib)
             if masked:
                 _premasked[dx.data_ptr()] = (x.data_ptr(), dx._version, tuple(dx.shape))
             upconv_stats_s2d["backwards"] += 1
