@@ -591,6 +591,37 @@ int ynet_rot_coords(double* xy, long long n, double cx, double cy, double r00, d
  * trajectory of the batch read.  n and batch_stride multiples of 4, 16-byte aligned. */
 int ynet_batch_sum(const float* x, float* y, int B, long long n, long long batch_stride, void* stream);
 
+/* ---- gradients with respect to the network input (saliency) ------------------------------------------------------------------ */
+/* The data gradient of the FIRST 3 x 3 convolution (padding 1) of the encoder, i.e. d loss / d input, for forward_test(decision =
+ * 'loss') and plot_saliency_maps (models/trainer.py:354-516, evaluator/visualization.py:1565).  The convolution reads the channel
+ * concatenation [scene c_s | motion c_m] (ops.lazy_cat of models/ynet.py:574, network 'original'); Y-Net-Mod's two first convolutions
+ * (scene_stages[0]: c_m = 0, motion_stages[0]: c_s = 0) are served one destination each.
+ *   dy [B][cout][H][W]; relu_of (may be NULL): the layer's post-ReLU output [B][cout][H][W] -- dy counts where relu_of > 0 only;
+ *   wp = ynet_pack_weight(W, mode 1) of the layer's filter (or the LoRA-composed pack the layer keeps);
+ *   d_motion [B][c_m][H][W] per image (NULL: not wanted);
+ *   d_scene [1][c_s][H][W] = the SUM over the batch of the per-image gradients -- the backward of `semantic_img.expand(B, ...)`
+ *   (utils/train_epoch.py:87) inside the launch (NULL: not wanted).  Summed in a fixed order: image order within chunks of 4, the chunk
+ *   partials (workspace, ynet_input_grad_workspace_floats floats; may be NULL when B <= 4) in chunk order by a second launch.  No atomics:
+ *   the same bits every run.
+ * Served: c_s in {0, 6, 16 (use_features_only)}, c_m in {0, 5, 8} (obs_len), cout in {8, 16, 32, 64}, H and W multiples of 32;
+ * anything else is refused (ynet_last_error).  64-bit offsets throughout (tensors beyond 2 and 4 GiB). */
+int ynet_input_grad_supported(int B, int H, int W, int cout, int c_s, int c_m);
+long long ynet_input_grad_workspace_floats(int B, int H, int W, int c_s);
+int ynet_input_grad(const float* dy, const float* relu_of, const float* wp, float* d_scene, float* d_motion, float* workspace, int B, int H,
+                    int W, int cout, int c_s, int c_m, void* stream);
+/* Backward of the waypoint pyramid [x, AvgPool2d(2)(x), ..., AvgPool2d(2^(nlev-1))(x)] (models/trainer.py:497-500, where x is the
+ * PREDICTED goal map and the gradient flows back into it): dx [N][H][W] = sum over levels l of grads[l][n][h >> l][w >> l] / 4^l, in
+ * level order.  grads: a HOST array of nlev (1..6) device pointers, level l of size [N][H >> l][W >> l]; grads[0] may be NULL (zero). */
+int ynet_avgpool_pyramid_bwd(const float* const* grads, int nlev, float* dx, long long N, int H, int W, void* stream);
+/* forward_test's noisy input (models/trainer.py:380-381, 472-479): out = x + N(0, 1) * frac * (max(x) - min(x)) over the n elements of
+ * x, the min / max reduced on the device (two launches; workspace of ynet_range_noise_workspace_floats() floats).  N(0, 1) by
+ * Box-Muller in fp64 from the Philox4x32-10 of ynet_multinomial: key = (seed low word, seed high word), element i draws
+ * u1 from counter (i low word, i high word, 0, 2) and u2 from (i low word, i high word, 1, 2), u as for ynet_multinomial; the noise is
+ * (float)(sqrt(-2 ln u1) cos(2 pi u2)) * std.  Reproducible from the seed alone; NOT bit-compatible with torch's normal_ (its
+ * Philox offsets and transform are the generator's own) -- the reference's draws cannot be replayed. */
+long long ynet_range_noise_workspace_floats(void);
+int ynet_add_range_noise(const float* x, float* out, long long n, float frac, unsigned long long seed, float* workspace, void* stream);
+
 /* ---- optimizer step --------------------------------------------------------------------------- */
 /* torch.optim.Adam / AdamW (models/trainer.py:182: Adam(lr)) for ALL parameters in two launches -- used inside captured training
  * steps, where torch's fused multi-tensor form costs 6 launches (0.18 ms alone on the GPU for a fully trainable Y-Net).  Same update

@@ -1,8 +1,9 @@
 """YNetTrainer on MI355X (mirror of models/trainer.py: same public methods, freeze policy,
 optimizer, log lines and checkpoint format).
 
-Reference: __init__ 46-75, _train 80-293 (freeze table 116-195), _test 299-352, prepare_data 518-584,
-load_params / save_params / load_separated_params 586-614, mark_*_bias_trainable 20-42.
+Reference: __init__ 46-75, _train 80-293 (freeze table 116-195), _test 299-352, forward_test / _forward_test /
+_forward_batch 354-516, prepare_data 518-584, load_params / save_params / load_separated_params 586-614,
+mark_*_bias_trainable 20-42.  ``saliency`` (new) wraps forward_test(decision='loss') and one backward.
 Differences, all outside the arithmetic: image files are not decoded here (cv2/smp are out of scope) —
 ``prepare_data`` takes a dict {scene_id: float tensor [C,H,W]} in place of an image directory; an
 optional ``dp`` (dist.DataParallel) shards batches over the GPUs of a node.
@@ -22,7 +23,7 @@ from tqdm import tqdm
 from .. import ops
 from ..utils.dataloader import SceneDataset, scene_collate
 from ..utils.evaluate import evaluate
-from ..utils.image_utils import (analytic_dist_template, analytic_gaussian_template, create_dist_mat,
+from ..utils.image_utils import (draw_seed, gather_patches, analytic_dist_template, analytic_gaussian_template, create_dist_mat,
                                  create_gaussian_heatmap_template)
 from ..utils.train_epoch import train_epoch
 from .ynet import YNet
@@ -55,6 +56,19 @@ class HipBCEWithLogitsLoss(nn.Module):
                    f"for the upstream gradient {fused[2]} but expected_grad is now {float(self.expected_grad)}")
                 + "; compute the maps outside announce_bce_target (or set YNET_PRED_BCE=0) for any other use")
         return ops.bce_with_logits(input, target, self.expected_grad)
+
+
+def _hip_criterion(criterion, loss_scale):
+    """The criterion _forward_batch builds (models/trainer.py:374: nn.BCEWithLogitsLoss()) on the HIP BCE kernels: mean over the
+    elements, the gradient of the logits written in the loss's own pass for the upstream gradient loss_scale (ops.bce_with_logits).
+    Any other configuration is refused -- there is no ATen path."""
+    if isinstance(criterion, HipBCEWithLogitsLoss):
+        criterion.expected_grad = float(loss_scale)
+        return criterion
+    if (type(criterion) is nn.BCEWithLogitsLoss and criterion.reduction == "mean" and criterion.weight is None
+            and criterion.pos_weight is None):
+        return lambda x, t: ops.bce_with_logits(x, t, float(loss_scale))
+    raise NotImplementedError(f"_forward_batch: criterion {criterion!r} has no HIP kernel (nn.BCEWithLogitsLoss() with the defaults only)")
 
 
 def _mark_bias(module):
@@ -295,6 +309,140 @@ class YNetTrainer:
         avg_fde = sum(self.eval_FDE) / len(self.eval_FDE)
         print(f"\nAverage performance (by {n_round}): \nTest ADE: {avg_ade} \nTest FDE: {avg_fde}")
         return avg_ade, avg_fde, list_metrics, list_trajs
+
+    # ------------------------------------------------------------------------------------------
+    def forward_test(self, df_test, image_path, set_input, noisy_std_frac):
+        return self._forward_test(df_test, image_path, set_input, noisy_std_frac, **self.params)
+
+    def _forward_test(self, df_test, image_path, set_input, noisy_std_frac, decision, dataset_name, obs_len, pred_len,
+                      resize_factor, use_raw_data, waypoints, kernlen, nsig, loss_scale, **kwargs):
+        """models/trainer.py:357-457 for the one scene of ``df_test`` (all its trajectories form one batch).
+
+        decision 'map':  (pred_goal_map, pred_traj_map, scene_raw_img) -- with ``noisy_std_frac``
+                         (pred_goal_map, pred_traj_map, scene_raw_img, noisy_scene_img, semantic_input_cat);
+        decision 'loss': (goal_loss, traj_loss, scene_raw_img[, noisy_scene_img]).
+        ``set_input`` names the inputs that receive a gradient: 'scene' (the scene image), 'semantic' (the semantic map after the
+        segmentation / semantic adapter: a leaf of its own, the scene then gets none), 'traj' (the observed-trajectory heat-maps).
+        They are autograd leaves, so ``(goal_loss + traj_loss).backward()`` fills their ``.grad``; ``self.forward_inputs`` holds
+        them by name after the call ('traj' is not among the returned values).  The reference passes ``False`` as set_input on its
+        'loss' branch (models/trainer.py:387, 400, 416) and raises TypeError there; this is what that branch evidently meant.
+        With ``noisy_std_frac`` every input named in set_input is replaced by a noisy copy x + N(0, (frac * (max - min))^2)
+        (ops.add_range_noise: drawn on the device from a seed of torch's default generator -- reproducible under torch.manual_seed,
+        NOT the draws of the reference's normal_), and that copy is the leaf; noisy_scene_img is the scene input actually fed.
+        The heat-maps are the analytic templates' (bit-identical to get_patch); the criterion the reference builds,
+        nn.BCEWithLogitsLoss(), runs on the HIP BCE kernels (ops.bce_with_logits)."""
+        if decision not in ("loss", "map"):
+            raise ValueError(f"No support for decision={decision}")
+        test_images, test_loader, self.homo_mat = self.prepare_data(
+            df_test, image_path, dataset_name, "test", obs_len, pred_len, resize_factor, use_raw_data)
+        if len(test_loader) == 0:
+            raise ValueError("No data is provided")
+        if len(test_loader) > 1:
+            raise ValueError(f"Received more than 1 scene ({len(test_loader)})")
+        input_template, gt_template = self.templates(kernlen, nsig)
+        criterion = nn.BCEWithLogitsLoss()
+        traj, _, scene_id = next(iter(test_loader))
+        scene_raw_img = test_images[scene_id].to(self.device).unsqueeze(0)
+        set_input = tuple(set_input) if set_input else ()
+        scene_raw_img.requires_grad_("scene" in set_input and not (noisy_std_frac is not None))
+        out = self._forward_batch(scene_raw_img, traj, input_template, gt_template, criterion, obs_len, pred_len, waypoints,
+                                  loss_scale, self.device, set_input, noisy_std_frac, decision == "map")
+        if decision == "loss":
+            goal_loss, traj_loss, noisy_scene_img = out[0], out[1], out[2]
+            if noisy_std_frac is not None:
+                return goal_loss, traj_loss, scene_raw_img, noisy_scene_img
+            return goal_loss, traj_loss, scene_raw_img
+        pred_goal_map, pred_traj_map, noisy_scene_img, semantic_input_cat = out
+        if noisy_std_frac is not None:
+            return pred_goal_map, pred_traj_map, scene_raw_img, noisy_scene_img, semantic_input_cat
+        return pred_goal_map, pred_traj_map, scene_raw_img
+
+    def _forward_batch(self, scene_raw_img, traj, input_template, gt_template, criterion, obs_len, pred_len, waypoints,
+                       loss_scale, device, set_input=None, noisy_std_frac=None, return_pred_map=False):
+        """models/trainer.py:459-516.  Returns (goal_loss, traj_loss, scene input fed) or, with return_pred_map,
+        (pred_goal_map, pred_traj_map, scene input fed, [semantic | observed] cat or None)."""
+        set_input = tuple(set_input) if set_input else ()
+        model = self.model.to(self.device)
+        network = self.params.get("network") if hasattr(self.params, "get") else None
+        if set_input and network == "embed":
+            raise NotImplementedError("input gradients of network='embed' (its first convolutions are the embeddings') are not served")
+        _, _, H, W = scene_raw_img.shape
+        coords = traj
+        ops.check_patch_windows(input_template.shape, coords, H, W)
+        observed_map = gather_patches(input_template, coords[:, :obs_len].reshape(-1, 2), H, W).view(-1, obs_len, H, W)
+        gt_future_map = gather_patches(gt_template, coords[:, obs_len:].reshape(-1, 2), H, W).view(-1, pred_len, H, W)
+        B = observed_map.shape[0]
+        scene_image = model.segmentation(scene_raw_img)
+        semantic_image = model.adapt_semantic(scene_image)
+        scene_leaf = "scene" in set_input or "semantic" in set_input
+        noisy = noisy_std_frac is not None
+        if noisy and scene_leaf:
+            semantic_image = ops.add_range_noise(semantic_image, noisy_std_frac, draw_seed()).requires_grad_()
+        elif "semantic" in set_input:
+            semantic_image = semantic_image.detach().requires_grad_()
+        if noisy and "traj" in set_input:
+            observed_map = ops.add_range_noise(observed_map, noisy_std_frac, draw_seed()).requires_grad_()
+        elif "traj" in set_input:
+            observed_map.requires_grad_()
+        self.forward_inputs = {"traj": observed_map}
+        if "semantic" in set_input or (noisy and scene_leaf):
+            self.forward_inputs["semantic"] = semantic_image
+        if "scene" in set_input:
+            self.forward_inputs["scene"] = semantic_image if noisy else scene_raw_img
+        sem_fed, obs_fed = semantic_image, observed_map
+        if network == "embed":      # utils/train_epoch.py:80-83 (the reference's _forward_batch skips it)
+            semantic_image = model.scene_embedding(semantic_image)
+            observed_map = model.motion_embedding(observed_map)
+        # one scene for every trajectory: broadcast, its gradient summed over the batch inside the first layer's backward
+        semantic_map = ops.BatchExpand(semantic_image, B) if B > 1 else semantic_image
+        features = model.pred_features(semantic_map, observed_map)
+        pred_goal_map = model.pred_goal(features)
+        bce = _hip_criterion(criterion, loss_scale)
+        goal_loss = bce(pred_goal_map, gt_future_map) * loss_scale
+        pred_waypoint_map = pred_goal_map[:, list(waypoints)]
+        pyramid = ops.avgpool_pyramid_grad(pred_waypoint_map, len(features))
+        traj_input = [ops.lazy_cat([f, g]) for f, g in zip(features, pyramid)]
+        pred_traj_map = model.pred_traj(traj_input)
+        traj_loss = bce(pred_traj_map, gt_future_map) * loss_scale
+        scene_fed = sem_fed if (noisy and scene_leaf) else scene_raw_img
+        if return_pred_map:
+            cat = None
+            if noisy:
+                with torch.no_grad():
+                    cat = torch.cat([sem_fed.detach().expand(B, -1, -1, -1), obs_fed.detach()], dim=1)
+            return pred_goal_map, pred_traj_map, scene_fed, cat
+        return goal_loss, traj_loss, scene_fed
+
+    def saliency(self, df_test, image_path, target="both", set_input=("scene", "traj")):
+        """Input-gradient saliency (the inputs of evaluator/visualization.py:1565 plot_saliency_maps): d loss / d input for
+        loss = goal_loss + traj_loss ('both'), goal_loss or traj_loss, from forward_test(decision='loss') and ONE backward.
+        Returns {name: gradient} for the names of ``set_input`` -- 'scene' / 'semantic' [C_s, H, W] (summed over the batch),
+        'traj' [B, obs_len, H, W] -- as device tensors.  The parameters' ``.grad`` fields are left as they were."""
+        if target not in ("both", "goal", "traj"):
+            raise ValueError(f"saliency: target must be 'both', 'goal' or 'traj', got {target!r}")
+        if isinstance(set_input, str) or not set_input or any(n not in ("scene", "traj", "semantic") for n in set_input) \
+                or len(set(set_input)) != len(tuple(set_input)):
+            raise ValueError(f"saliency: set_input must be a non-empty sequence of distinct names among 'scene', 'traj', 'semantic', "
+                             f"got {set_input!r}")
+        if "scene" in set_input and "semantic" in set_input:
+            raise ValueError("saliency: 'scene' and 'semantic' exclude each other (the semantic map is a leaf of its own)")
+        params = {k: v for k, v in self.params.items() if k != "decision"}
+        try:
+            return self._saliency_grads(df_test, image_path, target, tuple(set_input), params)
+        finally:
+            self.forward_inputs = {}
+            ops.release_stale_entries()      # (the graph of the call is gone by now)
+
+    def _saliency_grads(self, df_test, image_path, target, set_input, params):
+        goal_loss, traj_loss, _ = self._forward_test(df_test, image_path, set_input, None, "loss", **params)
+        loss = goal_loss + traj_loss if target == "both" else (goal_loss if target == "goal" else traj_loss)
+        leaves = [self.forward_inputs[n] for n in set_input]
+        grads = torch.autograd.grad(loss, leaves, allow_unused=True)
+        out = {}
+        for n, t, g in zip(set_input, leaves, grads):
+            g = torch.zeros_like(t) if g is None else g
+            out[n] = g[0] if n in ("scene", "semantic") else g
+        return out
 
     # ------------------------------------------------------------------------------------------
     def prepare_data(self, df, image_path, dataset_name, mode, obs_len, pred_len, resize_factor, use_raw_data,

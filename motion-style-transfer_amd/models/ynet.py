@@ -365,6 +365,10 @@ class YNetEncoderFusion(nn.Module):
         B = scene_map.shape[0]
         once = SHARED_SCENE_BRANCH and torch.is_tensor(scene_map) and B > 1 and scene_map.stride(0) == 0
         x = scene_map[:1] if once else scene_map
+        if isinstance(scene_map, ops.BatchExpand):
+            # (forward_test / saliency: the one-image scene itself enters the branch, so its gradient arrives summed over the batch)
+            once = SHARED_SCENE_BRANCH and B > 1
+            x = scene_map.tensor if (once or B == 1) else scene_map.expand()
         def walk(stages, x, out, tail_pooled):
             # (every stage but a branch's last is followed by a stage that opens with MaxPool2d; the branch's last output is pooled by
             # the first fused stage -- as part of a concatenation, so each part is pooled on its own there)

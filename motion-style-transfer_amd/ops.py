@@ -1222,6 +1222,9 @@ class _Conv2dFn(torch.autograd.Function):
         relu, scale, cache = meta["relu"], meta.get("scale", 1.0), meta["cache"]
         _need_gpu(weight, "conv2d weight")
         cout, cin, k, _ = weight.shape
+        if meta.get("bcast"):
+            # (one-image network inputs read by every image of the batch: batch stride 0, gradient summed by ynet_input_grad)
+            srcs = [s.expand(meta["batch"], -1, -1, -1) if f else s for s, f in zip(srcs, meta["bcast"])]
         descs, keep = [], []
         reps = meta.get("repeat") or [1] * len(srcs)
         for i, s in enumerate(srcs):
@@ -1335,7 +1338,12 @@ class _Conv2dFn(torch.autograd.Function):
             cur = torch.cuda.current_stream(dy.device)
             bkey, branch = _wgrad_stream(dy.device)
             branch.wait_stream(cur)
-        if any(need_src):
+        if any(need_src) and meta.get("input_grad") is not None:
+            # the network's own inputs (saliency, models/trainer.py:354-516): ynet_input_grad, batch sum of a broadcast scene inside
+            if ctx.w_key != _weight_key(weight, lora_a, lora_b):
+                raise RuntimeError("conv2d backward: a parameter was modified in place between forward and backward")
+            d_srcs = _input_grad_srcs(meta, dy, y, _cached(cache, weight, lora_a, lora_b, scale, "dgrad"), srcs, need_src)
+        elif any(need_src):
             if ctx.w_key != _weight_key(weight, lora_a, lora_b):
                 raise RuntimeError("conv2d backward: a parameter was modified in place between forward and backward")
             wp_d = _cached(cache, weight, lora_a, lora_b, scale, "dgrad")
@@ -1504,7 +1512,12 @@ def conv2d(x, weight, bias, relu: bool, cache: dict, lora_a=None, lora_b=None, s
     the 1-bit form of its ReLU mask, which that convolution's data gradient applies to what it writes (ynet_conv2d_relu_bits); an int:
     that next convolution's output channels -- where its data gradient will be a Winograd launch (which reads the float activation) no
     bits are written."""
-    parts = [p.expand() if isinstance(p, BatchExpand) else p for p in _parts(x)]      # (a fresh expand node per consumer)
+    raw = _parts(x)
+    route = _input_layer(raw, weight) if torch.is_grad_enabled() else None
+    if route is not None:
+        parts = [p.tensor if isinstance(p, BatchExpand) else p for p in raw]
+    else:
+        parts = [p.expand() if isinstance(p, BatchExpand) else p for p in raw]      # (a fresh expand node per consumer)
     # wino: the plain 16 / 32-channel large-map launches take the Winograd generation (conv2d_raw).  Its results differ from the
     # implicit GEMM's by fp32 rounding that is uncorrelated with the reference's own (the implicit GEMM sums in nearly the reference's
     # order).  Measured against the CPU oracle (tests/wino_margin.py): a training step's loss / ADE / FDE / per-trajectory read-outs
@@ -1518,7 +1531,154 @@ def conv2d(x, weight, bias, relu: bool, cache: dict, lora_a=None, lora_b=None, s
             raise NotImplementedError("conv2d: batch-repeated inputs are for inference (torch.no_grad) only")
         meta["repeat"] = [p.times if isinstance(p, BatchRepeat) else 1 for p in parts]
         parts = [p.tensor if isinstance(p, BatchRepeat) else p for p in parts]
+    if route is not None:
+        meta["input_grad"], meta["bcast"], meta["batch"] = route
     return _Conv2dFn.apply(meta, weight, bias, lora_a, lora_b, *parts)
+
+
+# ------------------------------------------------------------------------------------------------
+# gradients with respect to the network input (forward_test / saliency, models/trainer.py:354-516)
+# ------------------------------------------------------------------------------------------------
+SCENE_CHANNELS, MOTION_CHANNELS = (6, 16), (5, 8)      # n_semantic_classes (16: use_features_only), obs_len
+
+
+def _input_layer(parts, weight):
+    """((c_s, c_m), broadcast flags, B) when the sources of a convolution are network inputs that want a gradient -- autograd leaves,
+    as forward_test / saliency make them -- in a layout ynet_input_grad serves: [scene | motion], [scene] or [motion], the scene one
+    image (an ops.BatchExpand of it for B > 1).  None otherwise, in particular in every training step (no conv input there is a leaf
+    that requires grad): the convolution then takes its usual path."""
+    ts = [p.tensor if isinstance(p, BatchExpand) else p for p in parts]
+    if len(ts) > 2 or not all(torch.is_tensor(t) for t in ts) or not any(t.requires_grad for t in ts):
+        return None
+    if any(t.requires_grad and not t.is_leaf for t in ts) or weight.shape[2] != 3 or not all(t.is_cuda and t.is_contiguous() for t in ts):
+        return None
+    B = max(int(p.shape[0]) for p in parts)
+    if len(ts) == 2:
+        roles = ("s", "m")
+    else:
+        roles = ("s",) if ts[0].shape[1] in SCENE_CHANNELS else ("m",)
+    cs = cm = 0
+    bcast = []
+    for p, t, r in zip(parts, ts, roles):
+        if r == "s":
+            if not (isinstance(p, BatchExpand) or t.shape[0] == 1) or t.shape[1] not in SCENE_CHANNELS:
+                return None
+            cs = int(t.shape[1])
+            bcast.append(B > 1)
+        else:
+            if isinstance(p, BatchExpand) or t.shape[0] != B or t.shape[1] not in MOTION_CHANNELS:
+                return None
+            cm = int(t.shape[1])
+            bcast.append(False)
+    H, W = int(ts[0].shape[2]), int(ts[0].shape[3])
+    if not _lib().ynet_input_grad_supported(B, H, W, int(weight.shape[0]), cs, cm):
+        return None
+    return (cs, cm), bcast, B
+
+
+def _input_grad_srcs(meta, dy, y, wp, srcs, need_src):
+    """The gradients of a convolution's input sources by ynet_input_grad (see _input_layer): per image for the motion maps, summed over
+    the batch for the (one-image) scene."""
+    (cs, cm), B = meta["input_grad"], meta["batch"]
+    _, cout, H, W = dy.shape
+    out = [None] * len(srcs)
+    d_scene = d_motion = None
+    for i in range(len(srcs)):
+        scene = i == 0 and cs > 0
+        if need_src[i]:
+            out[i] = torch.empty((1, cs, H, W) if scene else (B, cm, H, W), device=dy.device, dtype=torch.float32)
+            if scene:
+                d_scene = out[i]
+            else:
+                d_motion = out[i]
+    lib = _lib()
+    ws = None
+    n_ws = lib.ynet_input_grad_workspace_floats(B, H, W, cs) if d_scene is not None else 0
+    if n_ws > 0:
+        ws = torch.empty(n_ws, device=dy.device, dtype=torch.float32)
+    L.check(lib.ynet_input_grad(dy.data_ptr(), None if y is None else y.data_ptr(), wp.data_ptr(),
+                                None if d_scene is None else d_scene.data_ptr(), None if d_motion is None else d_motion.data_ptr(),
+                                None if ws is None else ws.data_ptr(), B, H, W, cout, cs, cm, _stream()), lib)
+    return out
+
+
+def input_grad(dy: torch.Tensor, wp: torch.Tensor, c_s: int, c_m: int, relu_of=None, want_scene: bool = True, want_motion: bool = True):
+    """(d_scene [1, c_s, H, W] summed over the batch, d_motion [B, c_m, H, W]) of a first 3 x 3 convolution from its output gradient dy
+    [B, cout, H, W] and its mode-1 packed filter wp (pack_weight(w, 1)); relu_of: the post-ReLU output (dy counts where it is > 0)."""
+    _need_gpu(dy, "input_grad dy")
+    _need_gpu(wp, "input_grad filter")
+    if relu_of is not None:
+        _need_gpu(relu_of, "input_grad relu_of")
+        if relu_of.shape != dy.shape:
+            raise ValueError(f"input_grad: relu_of {tuple(relu_of.shape)} does not match dy {tuple(dy.shape)}")
+        relu_of = relu_of.contiguous()
+    dy = dy.contiguous()
+    B, cout, H, W = dy.shape
+    lib = _lib()
+    if not lib.ynet_input_grad_supported(B, H, W, cout, c_s, c_m):
+        raise ValueError(f"input_grad: shape not served (B {B}, {H}x{W}, cout {cout}, scene {c_s}, motion {c_m})")
+    d_scene = torch.empty((1, c_s, H, W), device=dy.device, dtype=torch.float32) if (want_scene and c_s) else None
+    d_motion = torch.empty((B, c_m, H, W), device=dy.device, dtype=torch.float32) if (want_motion and c_m) else None
+    n_ws = lib.ynet_input_grad_workspace_floats(B, H, W, c_s) if d_scene is not None else 0
+    ws = torch.empty(n_ws, device=dy.device, dtype=torch.float32) if n_ws > 0 else None
+    L.check(lib.ynet_input_grad(dy.data_ptr(), None if relu_of is None else relu_of.data_ptr(), wp.data_ptr(),
+                                None if d_scene is None else d_scene.data_ptr(), None if d_motion is None else d_motion.data_ptr(),
+                                None if ws is None else ws.data_ptr(), B, H, W, cout, c_s, c_m, _stream()), lib)
+    return d_scene, d_motion
+
+
+def avgpool_pyramid_grad(x: torch.Tensor, n_levels: int) -> List[torch.Tensor]:
+    """avgpool_pyramid(x, n_levels) whose levels pass their gradients back to x (ynet_avgpool_pyramid_bwd sums them in one launch)."""
+    _need_gpu(x, "avgpool_pyramid_grad")
+    return [x] + list(_PyramidFn.apply(x, n_levels)) if n_levels > 1 else [x]
+
+
+def release_stale_entries():
+    """Drop the per-step registry entries whose tensors are gone.  A forward / backward outside fold_skip_gradients() (forward_test,
+    YNetTrainer.saliency) registers pooled copies and Gaussian targets that only the next registration would sweep; the entries
+    hold device tensors (the pooled maps, the target positions).  Not for use inside a step."""
+    for reg in (_pooled_outputs, _blob_targets, _relu_outputs, _s2d_wanted):
+        for k in [k for k, e in reg.items() if e[0]() is None]:
+            del reg[k]
+    for k in [k for k, e in _deferred.items() if e["ref"]() is None]:
+        del _deferred[k]
+    for k in [k for k, e in _skip_registry.items() if e.ref() is None or e.consumed]:
+        del _skip_registry[k]
+
+
+def add_range_noise(x: torch.Tensor, frac: float, seed: int) -> torch.Tensor:
+    """x + N(0, 1) * frac * (max(x) - min(x)) (models/trainer.py:380-381, 472-479), min / max and the draw on the device
+    (ynet_add_range_noise: Philox4x32-10 + Box-Muller, reproducible from `seed`; not the stream of torch's normal_)."""
+    _need_gpu(x, "add_range_noise")
+    x = x.detach().contiguous()
+    lib = _lib()
+    out = torch.empty_like(x)
+    ws = torch.empty(lib.ynet_range_noise_workspace_floats(), device=x.device, dtype=torch.float32)
+    L.check(lib.ynet_add_range_noise(x.data_ptr(), out.data_ptr(), x.numel(), float(frac), int(seed) & 0xFFFFFFFFFFFFFFFF, ws.data_ptr(),
+                                     _stream()), lib)
+    return out
+
+
+class _PyramidFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, n_levels):
+        ctx.shape = tuple(x.shape)
+        return tuple(avgpool_pyramid(x, n_levels)[1:])
+
+    @staticmethod
+    def backward(ctx, *gs):
+        N, C, H, W = ctx.shape
+        dev = next(g.device for g in gs if g is not None) if any(g is not None for g in gs) else None
+        if dev is None:
+            return None, None
+        levels = [torch.zeros((N, C, H >> (i + 1), W >> (i + 1)), device=dev, dtype=torch.float32) if g is None else g.contiguous()
+                  for i, g in enumerate(gs)]
+        # (level 0 of ynet_avgpool_pyramid_bwd is x's own gradient: none here, autograd adds that direct path itself)
+        dx = torch.empty(ctx.shape, device=dev, dtype=torch.float32)
+        ptrs = (_VP * (len(levels) + 1))(None, *[g.data_ptr() for g in levels])
+        lib = _lib()
+        L.check(lib.ynet_avgpool_pyramid_bwd(ctypes.cast(ptrs, L.PP), len(levels) + 1, dx.data_ptr(), N * C, H, W, _stream()), lib)
+        return dx, None
 
 
 # ------------------------------------------------------------------------------------------------
