@@ -562,6 +562,20 @@ int ynet_multinomial_devseed(const float* prob, long long rows, long long row_st
 int ynet_cws_prior(const float* sig, long long sig_batch_stride, int n_persons, const float* mean_xy, const float* dist_xy,
                    int rows, int H, int W, float sigma_factor, float ratio, int rot, float* out_map, float* out_xy,
                    void* stream);
+/* Scoring and ranking of the K = n_goal * n_traj sampled futures of every agent, for a forecast without ground truth (predict()):
+ * the samples are the way-points utils/evaluate.py:229-266 draws and the trajectories its K decoder passes read out; a sample is
+ * (x, y) = (column, row) of the map, the convention of `sampling` (utils/image_utils.py:110-135).  All arrays contiguous:
+ *   prob [B][n_wp][H][W]                 the output of ynet_sigmoid_temp (B * n_wp * H * W may exceed 2^31: 64-bit offsets)
+ *   waypoint_samples [K][B][n_wp][2], trajs [K][B][pred_len][2]      fp32, 8-byte aligned
+ *   score_k = sum over w = 0 .. n_wp - 1, in this order and in fp32, of logf(prob[b][w][rint(y)][rint(x)] + 1e-12f)
+ *   order [B][K] int32: the sample indices by descending score, equal scores by ascending index
+ *   score [B][K] = score of sample order[b][r] (i.e. sorted), ranked [B][K][pred_len][2] = trajs[order[b][r]][b] * inv_resize_factor
+ *   (inv_resize_factor = (float)(1.0 / resize_factor): original-image pixels), ranked_goals [B][K][n_wp][2] = the way-points, permuted alike.
+ * One wavefront per agent, one sample per lane: 1 <= K <= 64, anything else is refused.  *status (device int, zero it first) becomes 1
+ * if a sample rounds to a pixel outside the H x W map; such a sample adds nothing to its score and no memory outside the map is read. */
+int ynet_score_rank_samples(const float* prob, const float* waypoint_samples, const float* trajs, int B, int K, int n_wp, int pred_len,
+                            int H, int W, float inv_resize_factor, float* score, int* order, float* ranked, float* ranked_goals,
+                            int* status, void* stream);
 
 /* ---- scene pre-processing without OpenCV / the segmentation backbone (the pinnable part) ------------- */
 /* pad (utils/image_utils.py:95-107): N planes H x W -> Hp x Wp, zero border at the bottom / right (cv2.copyMakeBorder,

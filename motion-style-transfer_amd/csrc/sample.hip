@@ -6,6 +6,7 @@
 //   multinomial_cdf_kernel    the replacement=True form (TTST's 10000 thresholded goal samples, utils/evaluate.py:137-139)
 //   cws_prior_kernel          torch_multivariate_gaussian_heatmap x sigmoid map, normalised, and its expectation
 //                             (conditioned waypoint sampling, utils/evaluate.py:9-34, 172-224)
+//   score_rank_kernel         the K sampled futures of an agent scored against the goal map and ranked (predict())
 //
 // Random numbers: Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11; the constants of Random123 / cuRAND / torch's
 // device generator), key = (seed & 0xffffffff, seed >> 32), counter = (element, 0, row, stream) with stream 0 for the
@@ -303,6 +304,87 @@ __global__ __launch_bounds__(256) void cws_prior_kernel(const float* __restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Scoring and ranking of the K sampled futures of an agent (predict(): utils/evaluate.py:229-266 without the ground
+// truth).  One wavefront per agent, sample k on lane k:
+//   score_k = sum over way-points w (in order, fp32) of logf(prob[b][w][y][x] + 1e-12f),  (x, y) = rint of the sample
+//   rank_k  = #{j : score_j > score_k  or  (score_j == score_k and j < k)}               (descending, ties to the lower index)
+// The ranks are counted in the wave with one broadcast per sample (no LDS storage, no atomics); ds_permute sends k to lane
+// rank_k, so lane r knows the sample that takes output row r.  Rows are copied as (x, y) pairs, lanes along the output.
+// A sample that rounds to a pixel outside the map is not read: *status becomes 1 (every lane that sees one writes the same value).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int score_order_key(float s) {
+    // a total order on the bits (a NaN score still gets a rank of its own): larger key = better sample
+    const int b = __float_as_int(s + 0.f);      // (-0 -> +0)
+    return b >= 0 ? b : (b ^ 0x7fffffff);
+}
+
+__global__ __launch_bounds__(256) void score_rank_kernel(const float* __restrict__ prob, const float* __restrict__ wps,
+                                                         const float* __restrict__ trajs, int B, int K, int n_wp, int pred_len, int H,
+                                                         int W, float inv_resize, float* __restrict__ score, int* __restrict__ order,
+                                                         float* __restrict__ ranked, float* __restrict__ ranked_goals,
+                                                         int* __restrict__ status) {
+    const int lane = threadIdx.x & 63;
+    const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;      // (whole waves leave; nothing below synchronises the workgroup)
+    const long long plane = (long long)H * W;
+    float s = 0.f;
+    if (lane < K) {
+        const float2* wp = reinterpret_cast<const float2*>(wps) + ((long long)lane * B + b) * n_wp;
+        const float* pb = prob + b * n_wp * plane;
+        bool bad = false;
+        for (int w = 0; w < n_wp; ++w) {
+            const float2 c = wp[w];
+            const float fx = rintf(c.x), fy = rintf(c.y);
+            if (fx >= 0.f && fx < (float)W && fy >= 0.f && fy < (float)H) {
+                s += logf(pb[w * plane + (long long)fy * W + (long long)fx] + 1e-12f);
+            } else {
+                bad = true;
+            }
+        }
+        if (bad) *status = 1;
+    }
+    // every cross-lane step below runs with all 64 lanes active: a shuffle reads nothing from a lane that has left
+    const int key = score_order_key(s);
+    int rank = 0;
+    for (int j = 0; j < K; ++j) {
+        const int kj = __shfl(key, j, 64);
+        rank += (kj > key || (kj == key && j < lane)) ? 1 : 0;
+    }
+    if (lane >= K) rank = lane;      // lanes past K keep their own number: the permutation stays one-to-one
+    const int src = __builtin_amdgcn_ds_permute(rank << 2, lane);      // lane r <- the sample whose rank is r
+    const float s_src = __shfl(s, src, 64);
+    if (lane < K) {
+        order[b * K + lane] = src;
+        score[b * K + lane] = s_src;
+    }
+    {
+        const float2* in = reinterpret_cast<const float2*>(trajs);
+        float2* out = reinterpret_cast<float2*>(ranked) + b * K * pred_len;
+        const int total = K * pred_len;
+        for (int i0 = 0; i0 < total; i0 += 64) {
+            const int i = i0 + lane, r = min(i, total - 1) / pred_len, t = i - r * pred_len;
+            const int k = __shfl(src, r, 64);
+            if (i < total) {
+                float2 v = in[((long long)k * B + b) * pred_len + t];
+                v.x *= inv_resize;
+                v.y *= inv_resize;
+                out[i] = v;
+            }
+        }
+    }
+    {
+        const float2* in = reinterpret_cast<const float2*>(wps);
+        float2* out = reinterpret_cast<float2*>(ranked_goals) + b * K * n_wp;
+        const int total = K * n_wp;
+        for (int i0 = 0; i0 < total; i0 += 64) {
+            const int i = i0 + lane, r = min(i, total - 1) / n_wp, w = i - r * n_wp;
+            const int k = __shfl(src, r, 64);
+            if (i < total) out[i] = in[((long long)k * B + b) * n_wp + w];
+        }
+    }
+}
+
 static int multinomial_impl(const float* prob, long long rows, long long row_stride, int n, int K, int replacement,
                             float rel_threshold, unsigned long long seed, const unsigned long long* seed_ptr, long long* out, int* status,
                             void* stream) {
@@ -353,6 +435,25 @@ int ynet_cws_prior(const float* sig, long long sig_batch_stride, int n_persons, 
     hipLaunchKernelGGL(cws_prior_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, sig, sig_batch_stride, n_persons,
                        mean_xy, dist_xy, H, W, sigma_factor, ratio, rot, out_map, out_xy);
     return ynet_check_launch("cws_prior");
+}
+
+// The K sampled futures of each agent, scored against the goal map and handed back best first (utils/evaluate.py:229-266 draws
+// and decodes them; utils/image_utils.py:110-135: a sample is (x, y) = (column, row) of the map).  Contiguous arrays; see the header.
+int ynet_score_rank_samples(const float* prob, const float* waypoint_samples, const float* trajs, int B, int K, int n_wp, int pred_len,
+                            int H, int W, float inv_resize_factor, float* score, int* order, float* ranked, float* ranked_goals,
+                            int* status, void* stream) {
+    YNET_REQUIRE(K >= 1 && K <= 64, "score_rank_samples: K = %d samples per agent; one wavefront ranks 1 .. 64", K);
+    YNET_REQUIRE(prob && waypoint_samples && trajs && score && order && ranked && ranked_goals && status,
+                 "score_rank_samples: null pointer");
+    YNET_REQUIRE(B > 0 && n_wp > 0 && pred_len > 0 && H > 0 && W > 0 && n_wp <= (1 << 16) && pred_len <= (1 << 16),
+                 "score_rank_samples: bad shape B=%d n_wp=%d pred_len=%d map %dx%d", B, n_wp, pred_len, H, W);
+    YNET_REQUIRE(inv_resize_factor > 0.f && inv_resize_factor < INFINITY, "score_rank_samples: 1 / resize_factor must be positive and finite");
+    YNET_REQUIRE(((reinterpret_cast<uintptr_t>(waypoint_samples) | reinterpret_cast<uintptr_t>(trajs) | reinterpret_cast<uintptr_t>(ranked) |
+                   reinterpret_cast<uintptr_t>(ranked_goals)) & 7) == 0,
+                 "score_rank_samples: the (x, y) arrays must be 8-byte aligned");
+    hipLaunchKernelGGL(score_rank_kernel, dim3((unsigned)ceil_div(B, 4)), dim3(256), 0, (hipStream_t)stream, prob, waypoint_samples, trajs,
+                       B, K, n_wp, pred_len, H, W, inv_resize_factor, score, order, ranked, ranked_goals, status);
+    return ynet_check_launch("score_rank_samples");
 }
 
 }  // extern "C"

@@ -3,7 +3,8 @@ optimizer, log lines and checkpoint format).
 
 Reference: __init__ 46-75, _train 80-293 (freeze table 116-195), _test 299-352, forward_test / _forward_test /
 _forward_batch 354-516, prepare_data 518-584, load_params / save_params / load_separated_params 586-614,
-mark_*_bias_trainable 20-42.  ``saliency`` (new) wraps forward_test(decision='loss') and one backward.
+mark_*_bias_trainable 20-42.  ``saliency`` (new) wraps forward_test(decision='loss') and one backward; ``predict`` (new) forecasts
+from the observed steps alone: all K samples, scored and ranked (utils/predict.py).
 Differences, all outside the arithmetic: image files are not decoded here (cv2/smp are out of scope) —
 ``prepare_data`` takes a dict {scene_id: float tensor [C,H,W]} in place of an image directory; an
 optional ``dp`` (dist.DataParallel) shards batches over the GPUs of a node.
@@ -309,6 +310,64 @@ class YNetTrainer:
         avg_fde = sum(self.eval_FDE) / len(self.eval_FDE)
         print(f"\nAverage performance (by {n_round}): \nTest ADE: {avg_ade} \nTest FDE: {avg_fde}")
         return avg_ade, avg_fde, list_metrics, list_trajs
+
+    # ------------------------------------------------------------------------------------------
+    def predict(self, df_obs, image_path_or_images, return_maps=False):
+        """Forecasts WITHOUT ground truth (new; the reference's test() needs obs_len + pred_len rows per agent and its plotting
+        helpers re-run it): the K = n_goal * n_traj sampled futures of every agent, scored against the goal map and ranked
+        (utils/predict.py).  ``df_obs``: a DataFrame with EXACTLY obs_len rows per metaId (columns metaId, sceneId, x, y in
+        original-image pixels, scaled by resize_factor as SceneDataset does), or a dict {scene_id: [N, obs_len, 2] array} of such
+        tracks (metaIds are then numbered in order).  ``image_path_or_images``: as for test(), the dict {scene_id: tensor}.
+        -> ({scene_id: dict of device tensors, see utils.predict.predict}, DataFrame [metaId, sceneId, rank, score])."""
+        return self._predict(df_obs, image_path_or_images, return_maps=return_maps, **self.params)
+
+    def _predict(self, df_obs, image_path, dataset_name, resize_factor, obs_len, waypoints, n_goal, n_traj, temperature,
+                 batch_size=None, rel_threshold=0.002, use_TTST=False, use_CWS=False, CWS_params=None, use_raw_data=False,
+                 network=None, swap_semantic=False, return_maps=False, **kwargs):
+        import pandas as pd
+        from ..utils.predict import MAX_SAMPLES, predict
+        if dataset_name.lower() == "eth":
+            raise NotImplementedError("predict: ETH/UCY forecasts are in world coordinates (homographies read from data files): "
+                                      "out of the MI355X hot path, as in prepare_data")
+        if n_goal * n_traj > MAX_SAMPLES:
+            raise ValueError(f"predict: n_goal * n_traj = {n_goal * n_traj} samples per agent; the ranking kernel takes up to {MAX_SAMPLES}")
+        if isinstance(df_obs, dict):
+            rows, first = [], 0
+            for scene_id, tracks in df_obs.items():
+                xy = np.asarray(tracks.detach().cpu() if torch.is_tensor(tracks) else tracks, dtype=np.float64)
+                if xy.ndim != 3 or xy.shape[2] != 2:
+                    raise ValueError(f"predict: scene {scene_id}: expected [N, obs_len, 2] tracks, got {xy.shape}")
+                if xy.shape[1] != obs_len:
+                    raise ValueError(f"predict: scene {scene_id}: {xy.shape[1]} steps per agent, obs_len is {obs_len}: pass exactly the "
+                                     f"observed steps (a longer track is never cut silently)")
+                ids = np.repeat(np.arange(first, first + xy.shape[0]), obs_len)
+                rows.append(pd.DataFrame({"metaId": ids, "sceneId": scene_id, "x": xy[..., 0].reshape(-1), "y": xy[..., 1].reshape(-1)}))
+                first += xy.shape[0]
+            if not rows:
+                raise ValueError("predict: no data is provided")
+            df_obs = pd.concat(rows, ignore_index=True)
+        counts = df_obs.groupby("metaId", sort=False).size()
+        if len(counts) == 0:
+            raise ValueError("predict: no data is provided")
+        if (counts != obs_len).any():
+            bad = counts[counts != obs_len]
+            raise ValueError(f"predict: every metaId needs exactly obs_len = {obs_len} rows (the observed steps alone); metaId {bad.index[0]} has "
+                             f"{int(bad.iloc[0])}" + (f" and {len(bad) - 1} more differ" if len(bad) > 1 else ""))
+        # scenes: the label-map / padding path of prepare_data; tracks: SceneDataset with no future steps (scaled by resize_factor)
+        images, loader, _ = self.prepare_data(df_obs, image_path, dataset_name, "test", obs_len, 0, resize_factor, use_raw_data)
+        model = self.model.to(self.device)
+        input_template = self.templates()
+        results, frames = {}, []
+        for observed, meta, scene_id in loader:
+            res = predict(model, images[scene_id], observed, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
+                          use_TTST=use_TTST, use_CWS=use_CWS, rel_thresh=rel_threshold, CWS_params=CWS_params, network=network,
+                          swap_semantic=swap_semantic, batch_size=batch_size, return_maps=return_maps)
+            results[scene_id] = res
+            scores = res["scores"].cpu().numpy()
+            n, k = scores.shape
+            frames.append(pd.DataFrame({"metaId": np.repeat(meta[0].metaId.unique(), k), "sceneId": [scene_id] * (n * k),
+                                        "rank": np.tile(np.arange(k), n), "score": scores.reshape(-1)}))
+        return results, pd.concat(frames, ignore_index=True)
 
     # ------------------------------------------------------------------------------------------
     def forward_test(self, df_test, image_path, set_input, noisy_std_frac):

@@ -2709,6 +2709,51 @@ def cws_prior(sig: torch.Tensor, mean_xy: torch.Tensor, dist_xy: torch.Tensor, s
     return out_map, out_xy
 
 
+_score_status = {}
+
+
+def score_rank_samples(prob: torch.Tensor, waypoint_samples: torch.Tensor, trajs: torch.Tensor, resize_factor: float):
+    """The K sampled futures of every agent scored against the goal map and ranked, best first (ynet_score_rank_samples; the
+    samples of utils/evaluate.py:229-266, (x, y) as `sampling` returns them, utils/image_utils.py:110-135).
+    prob [B, n_wp, H, W] = sigmoid_temp(...), waypoint_samples [K, B, n_wp, 2], trajs [K, B, pred_len, 2], all contiguous fp32, K <= 64.
+    score_k = sum over the way-points of log(prob at the sampled pixel + 1e-12), in fp32.
+    -> (ranked [B, K, pred_len, 2] = trajs by descending score / resize_factor (original-image pixels), ranked_goals [B, K, n_wp, 2],
+        score_sorted [B, K], order [B, K] int32: the sample index of every row; equal scores keep the lower index first).
+    Not differentiable.  A sample outside the map raises (the call waits for its launch to learn that)."""
+    for t, what in ((prob, "prob"), (waypoint_samples, "waypoint_samples"), (trajs, "trajs")):
+        _need_gpu(t, "score_rank_samples " + what)
+    if prob.dim() != 4 or waypoint_samples.dim() != 4 or trajs.dim() != 4:
+        raise ValueError("score_rank_samples: expected prob [B, n_wp, H, W], waypoint_samples [K, B, n_wp, 2] and trajs [K, B, pred_len, 2]")
+    B, n_wp, H, W = prob.shape
+    K, pred_len = waypoint_samples.shape[0], trajs.shape[2]
+    if tuple(waypoint_samples.shape) != (K, B, n_wp, 2) or tuple(trajs.shape) != (K, B, pred_len, 2):
+        raise ValueError(f"score_rank_samples: waypoint_samples {tuple(waypoint_samples.shape)} / trajs {tuple(trajs.shape)} do not go with "
+                         f"prob {tuple(prob.shape)} (expected [K, {B}, {n_wp}, 2] and [K, {B}, pred_len, 2])")
+    for t, what in ((prob, "prob"), (waypoint_samples, "waypoint_samples"), (trajs, "trajs")):
+        if not t.is_contiguous():
+            raise ValueError(f"score_rank_samples: {what} is not contiguous (strides {t.stride()}); the kernel addresses dense arrays")
+    if not float(resize_factor) > 0:
+        raise ValueError("score_rank_samples: the resize factor must be positive")
+    dev = prob.device
+    with torch.no_grad():
+        prob, waypoint_samples, trajs = prob.detach(), waypoint_samples.detach(), trajs.detach()
+        ranked = torch.empty((B, K, pred_len, 2), device=dev, dtype=torch.float32)
+        ranked_goals = torch.empty((B, K, n_wp, 2), device=dev, dtype=torch.float32)
+        score = torch.empty((B, K), device=dev, dtype=torch.float32)
+        order = torch.empty((B, K), device=dev, dtype=torch.int32)
+        st = _status_flag(_score_status, dev)
+        # x / resize_factor as torch divides a float tensor by a Python number on the device: the reciprocal taken in double, rounded to fp32, one product
+        inv = float(np.float32(1.0 / float(resize_factor)))
+        lib = _lib()
+        L.check(lib.ynet_score_rank_samples(prob.data_ptr(), waypoint_samples.data_ptr(), trajs.data_ptr(), B, K, n_wp, pred_len, H, W, inv,
+                                            score.data_ptr(), order.data_ptr(), ranked.data_ptr(), ranked_goals.data_ptr(), st.data_ptr(),
+                                            _stream()), lib)
+        if int(st.item()) != 0:
+            st.zero_()
+            raise RuntimeError(f"score_rank_samples: a sample lies outside the {H}x{W} map")
+    return ranked, ranked_goals, score, order
+
+
 def check_patch_status():
     """Raise if a device-side coordinate ever left the template (checked at sync points)."""
     for dev, st in _patch_status.items():

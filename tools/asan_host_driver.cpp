@@ -206,6 +206,9 @@ int main() {
     EXPECT_REJECT(ynet_multinomial(cfp, 1, 4, 4, 99, 0, 0.f, 1ull, (long long*)dummy, &status, nullptr));
     EXPECT_REJECT(ynet_multinomial(cfp, 1, 4, 4, 1, 0, 2.f, 1ull, (long long*)dummy, &status, nullptr));
     EXPECT_REJECT(ynet_cws_prior(cfp, 4, 1, cfp, cfp, 1, 2, 2, 0.f, 1.f, 0, fp, fp, nullptr));
+    EXPECT_REJECT(ynet_score_rank_samples(cfp, cfp, cfp, 2, 65, 1, 12, 8, 8, 4.f, fp, &status, fp, fp, &status, nullptr));      // K > 64
+    EXPECT_REJECT(ynet_score_rank_samples(cfp, cfp, cfp, 2, 0, 1, 12, 8, 8, 4.f, fp, &status, fp, fp, &status, nullptr));
+    EXPECT_REJECT(ynet_score_rank_samples(cfp, cfp, cfp, 2, 20, 1, 12, 8, 8, 0.f, fp, &status, fp, fp, &status, nullptr));
     EXPECT_REJECT(ynet_resize_nearest(nullptr, (int*)dummy, 4, 4, 2, 2, 0.5, 0.5, nullptr));
     EXPECT_REJECT(ynet_resize_nearest((const int*)dummy, (int*)dummy, 4, 4, 2, 2, 0.0, 0.5, nullptr));      // factor 0
     EXPECT_REJECT(ynet_upconv_dgrad_ring(nullptr, 0, cfp, nullptr, 0, fp, 0, 1, 64, 32, 8, 8, nullptr));
