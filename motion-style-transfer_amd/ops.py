@@ -211,6 +211,12 @@ def _plane_desc(t: torch.Tensor, what: str):
     return t, c, (st[0] if b > 1 else c * h * w)
 
 
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    """A contiguous tensor on a 16-byte boundary: `.contiguous()` hands a contiguous view back as it is, wherever in its buffer it starts."""
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
 def _arrays(descs):
     n = len(descs)
     ptrs = (_VP * n)(*[d[0] for d in descs])
@@ -2315,7 +2321,7 @@ def softargmax2d(x: torch.Tensor) -> torch.Tensor:
     t, c, bs = _plane_desc(x.detach(), "softargmax")
     B, _, H, W = t.shape
     if W % 4 == 0 and (bs % 4 or (H * W) % 4 or t.data_ptr() % 16):
-        t = t.contiguous()
+        t = _aligned16(t)
         bs = c * H * W
     out = torch.empty((B, c, 2), device=t.device, dtype=torch.float32)
     lib = _lib()
@@ -2330,6 +2336,8 @@ def train_readout(pred_traj_map: torch.Tensor, pred_goal_map: torch.Tensor, gt_f
         _need_gpu(t, "train_readout " + n)
     tm, gm = pred_traj_map.detach().contiguous(), pred_goal_map.detach().contiguous()
     B, P, H, W = tm.shape
+    if W % 4 == 0:          # (16-byte loads)
+        tm, gm = _aligned16(tm), _aligned16(gm)
     if tuple(gm.shape[0:1] + gm.shape[2:]) != (B, H, W) or tuple(gt_future.shape) != (B, P, 2):
         raise ValueError(f"train_readout: shapes {tuple(tm.shape)}, {tuple(gm.shape)}, {tuple(gt_future.shape)} do not fit")
     gt = gt_future.detach().contiguous()
@@ -2373,7 +2381,7 @@ def pred_softargmax(x: torch.Tensor, weight: torch.Tensor, bias) -> torch.Tensor
     t, cin, bs = _plane_desc(x.detach(), "pred_softargmax")
     B, _, H, W = t.shape
     if bs % 4 or t.data_ptr() % 16:
-        t = t.contiguous()
+        t = _aligned16(t)
         bs = cin * H * W
     cout = weight.shape[0]
     lib = _lib()
