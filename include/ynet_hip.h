@@ -576,6 +576,25 @@ int ynet_cws_prior(const float* sig, long long sig_batch_stride, int n_persons, 
 int ynet_score_rank_samples(const float* prob, const float* waypoint_samples, const float* trajs, int B, int K, int n_wp, int pred_len,
                             int H, int W, float inv_resize_factor, float* score, int* order, float* ranked, float* ranked_goals,
                             int* status, void* stream);
+/* ynet_score_rank_samples for a batch that the caller reordered before the sweep -- utils/predict.py: predict_styles() sorts the agents
+ * of a scene by style so that each style's adapted encoder convolutions run on contiguous rows; the samples are still those of
+ * utils/evaluate.py:229-266, (x, y) as `sampling` returns them (utils/image_utils.py:110-135).  Agent b of the batch reads prob,
+ * waypoint_samples and trajs at b, exactly as above, and writes score / order / ranked / ranked_goals at row out_row[b]: the results
+ * arrive in the caller's order from the ranking launch itself, with no second pass over [B][K][pred_len][2].
+ *   out_row [B] device int32, a permutation of 0 .. B - 1 (two agents naming one row would race; the host wrapper checks it).
+ * Scoring rule, tie rule, NaN rule, 64-bit offsets, alignment and the refusals (K outside 1 .. 64) are ynet_score_rank_samples'.
+ * *status (device int, zero it first): 1 if a sample rounds to a pixel outside the map (as above); 2 if an out_row entry lies outside
+ * 0 .. B - 1 -- that agent's wave then writes NOTHING (the entry is never used as an address) and the others are unaffected. */
+int ynet_score_rank_samples_rows(const float* prob, const float* waypoint_samples, const float* trajs, const int* out_row, int B, int K,
+                                 int n_wp, int pred_len, int H, int W, float inv_resize_factor, float* score, int* order, float* ranked,
+                                 float* ranked_goals, int* status, void* stream);
+/* dst[i][0 .. L) = src[idx[i]][0 .. L) for i = 0 .. n - 1: rows of L floats, both arrays dense, 64-bit offsets (src_rows * L may exceed
+ * 2^31).  Serves utils/predict.py: predict_styles(), which builds its style-sorted batch with it: the observed coordinates
+ * [N][obs_len * 2] and, inside each of the K slabs, the caller-order forced samples [K][N][n_wp * 2] (idx then holds slab * N + row).
+ * Indices may repeat.  Rows of even L behind 8-byte aligned src / dst move as 8-byte pairs.  idx [n] device int32.
+ * *status (device int, zero it first) becomes 1 if an index lies outside 0 .. src_rows - 1; that row of dst is left untouched and
+ * no memory outside src is read. */
+int ynet_gather_rows(const float* src, long long src_rows, const int* idx, float* dst, long long n, int L, int* status, void* stream);
 
 /* ---- scene pre-processing without OpenCV / the segmentation backbone (the pinnable part) ------------- */
 /* pad (utils/image_utils.py:95-107): N planes H x W -> Hp x Wp, zero border at the bottom / right (cv2.copyMakeBorder,

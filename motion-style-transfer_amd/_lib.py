@@ -156,6 +156,8 @@ SIGNATURES = {
     "ynet_multinomial_devseed": (c_i, [c_fp, c_ll, c_ll, c_i, c_i, c_i, c_f, c_fp, c_fp, c_fp, c_fp]),
     "ynet_cws_prior": (c_i, [c_fp, c_ll, c_i, c_fp, c_fp, c_i, c_i, c_i, c_f, c_f, c_i, c_fp, c_fp, c_fp]),
     "ynet_score_rank_samples": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "ynet_score_rank_samples_rows": (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "ynet_gather_rows": (c_i, [c_fp, c_ll, c_fp, c_fp, c_ll, c_i, c_fp, c_fp]),
     "ynet_input_grad_supported": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i]),
     "ynet_input_grad_workspace_floats": (c_ll, [c_i, c_i, c_i, c_i]),
     "ynet_input_grad": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_fp]),

@@ -7,6 +7,8 @@
 //   cws_prior_kernel          torch_multivariate_gaussian_heatmap x sigmoid map, normalised, and its expectation
 //                             (conditioned waypoint sampling, utils/evaluate.py:9-34, 172-224)
 //   score_rank_kernel         the K sampled futures of an agent scored against the goal map and ranked (predict())
+//   score_rank_rows_kernel    the same, every agent's results written to a row of the caller's choosing (predict_styles())
+//   gather_rows_kernel        dst[i, :] = src[idx[i], :]: a style-sorted batch built from the caller's rows (predict_styles())
 //
 // Random numbers: Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11; the constants of Random123 / cuRAND / torch's
 // device generator), key = (seed & 0xffffffff, seed >> 32), counter = (element, 0, row, stream) with stream 0 for the
@@ -385,6 +387,103 @@ __global__ __launch_bounds__(256) void score_rank_kernel(const float* __restrict
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// score_rank_kernel for a batch that was reordered before the sweep (predict_styles() sorts the agents by style): agent b of the
+// batch reads its own maps and samples at b and writes score / order / ranked / ranked_goals at row out_row[b], so the results land
+// in the caller's order from this launch (no pass over [N, K, pred_len, 2] afterwards).  Scoring rule, tie rule, NaN rule and the
+// lane layout are score_rank_kernel's.  out_row must be a permutation of 0 .. B - 1 (two agents with one row would race); an entry
+// outside 0 .. B - 1 is never used as an address: the agent's wave writes nothing and *status becomes 2.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void score_rank_rows_kernel(const float* __restrict__ prob, const float* __restrict__ wps,
+                                                              const float* __restrict__ trajs, const int* __restrict__ out_row, int B, int K,
+                                                              int n_wp, int pred_len, int H, int W, float inv_resize,
+                                                              float* __restrict__ score, int* __restrict__ order, float* __restrict__ ranked,
+                                                              float* __restrict__ ranked_goals, int* __restrict__ status) {
+    const int lane = threadIdx.x & 63;
+    const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;      // (whole waves leave; nothing below synchronises the workgroup)
+    const long long row = out_row[b];
+    if (row < 0 || row >= B) {      // (the same for all 64 lanes: the wave leaves as one)
+        *status = 2;
+        return;
+    }
+    const long long plane = (long long)H * W;
+    float s = 0.f;
+    if (lane < K) {
+        const float2* wp = reinterpret_cast<const float2*>(wps) + ((long long)lane * B + b) * n_wp;
+        const float* pb = prob + b * n_wp * plane;
+        bool bad = false;
+        for (int w = 0; w < n_wp; ++w) {
+            const float2 c = wp[w];
+            const float fx = rintf(c.x), fy = rintf(c.y);
+            if (fx >= 0.f && fx < (float)W && fy >= 0.f && fy < (float)H) {
+                s += logf(pb[w * plane + (long long)fy * W + (long long)fx] + 1e-12f);
+            } else {
+                bad = true;
+            }
+        }
+        if (bad) *status = 1;
+    }
+    const int key = score_order_key(s);
+    int rank = 0;
+    for (int j = 0; j < K; ++j) {
+        const int kj = __shfl(key, j, 64);
+        rank += (kj > key || (kj == key && j < lane)) ? 1 : 0;
+    }
+    if (lane >= K) rank = lane;
+    const int src = __builtin_amdgcn_ds_permute(rank << 2, lane);      // lane r <- the sample whose rank is r
+    const float s_src = __shfl(s, src, 64);
+    if (lane < K) {
+        order[row * K + lane] = src;
+        score[row * K + lane] = s_src;
+    }
+    {
+        const float2* in = reinterpret_cast<const float2*>(trajs);
+        float2* out = reinterpret_cast<float2*>(ranked) + row * K * pred_len;
+        const int total = K * pred_len;
+        for (int i0 = 0; i0 < total; i0 += 64) {
+            const int i = i0 + lane, r = min(i, total - 1) / pred_len, t = i - r * pred_len;
+            const int k = __shfl(src, r, 64);
+            if (i < total) {
+                float2 v = in[((long long)k * B + b) * pred_len + t];
+                v.x *= inv_resize;
+                v.y *= inv_resize;
+                out[i] = v;
+            }
+        }
+    }
+    {
+        const float2* in = reinterpret_cast<const float2*>(wps);
+        float2* out = reinterpret_cast<float2*>(ranked_goals) + row * K * n_wp;
+        const int total = K * n_wp;
+        for (int i0 = 0; i0 < total; i0 += 64) {
+            const int i = i0 + lane, r = min(i, total - 1) / n_wp, w = i - r * n_wp;
+            const int k = __shfl(src, r, 64);
+            if (i < total) out[i] = in[((long long)k * B + b) * n_wp + w];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// dst[i][:] = src[idx[i]][:] for n rows of `units` elements T (a float, or a float2 for rows of an even number of floats behind 8-byte
+// aligned pointers).  Grid-stride over the n * units elements, 64-bit offsets throughout.  An index outside 0 .. src_rows - 1 is never
+// used as an address: that row of dst is left as it was and *status becomes 1.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void gather_rows_kernel(const T* __restrict__ src, long long src_rows, const int* __restrict__ idx,
+                                                          T* __restrict__ dst, long long n, int units, int* __restrict__ status) {
+    const long long total = n * units, step = (long long)gridDim.x * 256;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += step) {
+        const long long i = e / units;
+        const long long r = idx[i];
+        if (r < 0 || r >= src_rows) {
+            *status = 1;
+            continue;
+        }
+        dst[e] = src[r * units + (e - i * units)];
+    }
+}
+
 static int multinomial_impl(const float* prob, long long rows, long long row_stride, int n, int K, int replacement,
                             float rel_threshold, unsigned long long seed, const unsigned long long* seed_ptr, long long* out, int* status,
                             void* stream) {
@@ -454,6 +553,47 @@ int ynet_score_rank_samples(const float* prob, const float* waypoint_samples, co
     hipLaunchKernelGGL(score_rank_kernel, dim3((unsigned)ceil_div(B, 4)), dim3(256), 0, (hipStream_t)stream, prob, waypoint_samples, trajs,
                        B, K, n_wp, pred_len, H, W, inv_resize_factor, score, order, ranked, ranked_goals, status);
     return ynet_check_launch("score_rank_samples");
+}
+
+// ynet_score_rank_samples for a batch the caller reordered before the sweep: agent b writes its results at row out_row[b] (see
+// score_rank_rows_kernel and the header).  out_row: B device ints, a permutation of 0 .. B - 1.
+int ynet_score_rank_samples_rows(const float* prob, const float* waypoint_samples, const float* trajs, const int* out_row, int B, int K,
+                                 int n_wp, int pred_len, int H, int W, float inv_resize_factor, float* score, int* order, float* ranked,
+                                 float* ranked_goals, int* status, void* stream) {
+    YNET_REQUIRE(K >= 1 && K <= 64, "score_rank_samples_rows: K = %d samples per agent; one wavefront ranks 1 .. 64", K);
+    YNET_REQUIRE(prob && waypoint_samples && trajs && out_row && score && order && ranked && ranked_goals && status,
+                 "score_rank_samples_rows: null pointer");
+    YNET_REQUIRE(B > 0 && n_wp > 0 && pred_len > 0 && H > 0 && W > 0 && n_wp <= (1 << 16) && pred_len <= (1 << 16),
+                 "score_rank_samples_rows: bad shape B=%d n_wp=%d pred_len=%d map %dx%d", B, n_wp, pred_len, H, W);
+    YNET_REQUIRE(inv_resize_factor > 0.f && inv_resize_factor < INFINITY,
+                 "score_rank_samples_rows: 1 / resize_factor must be positive and finite");
+    YNET_REQUIRE(((reinterpret_cast<uintptr_t>(waypoint_samples) | reinterpret_cast<uintptr_t>(trajs) | reinterpret_cast<uintptr_t>(ranked) |
+                   reinterpret_cast<uintptr_t>(ranked_goals)) & 7) == 0,
+                 "score_rank_samples_rows: the (x, y) arrays must be 8-byte aligned");
+    YNET_REQUIRE((reinterpret_cast<uintptr_t>(out_row) & 3) == 0, "score_rank_samples_rows: out_row must be 4-byte aligned");
+    hipLaunchKernelGGL(score_rank_rows_kernel, dim3((unsigned)ceil_div(B, 4)), dim3(256), 0, (hipStream_t)stream, prob, waypoint_samples,
+                       trajs, out_row, B, K, n_wp, pred_len, H, W, inv_resize_factor, score, order, ranked, ranked_goals, status);
+    return ynet_check_launch("score_rank_samples_rows");
+}
+
+// dst[i][0 .. L) = src[idx[i]][0 .. L): the row gather predict_styles() builds its style-sorted batch with (see the header).
+int ynet_gather_rows(const float* src, long long src_rows, const int* idx, float* dst, long long n, int L, int* status, void* stream) {
+    YNET_REQUIRE(src && idx && dst && status, "gather_rows: null pointer");
+    YNET_REQUIRE(src_rows > 0 && src_rows < (1ll << 31) && n > 0 && n < (1ll << 31) && L > 0,
+                 "gather_rows: bad shape src_rows=%lld n=%lld L=%d", src_rows, n, L);
+    YNET_REQUIRE(((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(idx)) & 3) == 0,
+                 "gather_rows: pointers must be 4-byte aligned");
+    const bool pairs = L % 2 == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 7) == 0;
+    const int units = pairs ? L / 2 : L;
+    const long long blocks = (n * units + 255) / 256;
+    const dim3 grid((unsigned)(blocks < (1ll << 16) ? blocks : (1ll << 16)));
+    if (pairs) {
+        hipLaunchKernelGGL(gather_rows_kernel<float2>, grid, dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float2*>(src), src_rows,
+                           idx, reinterpret_cast<float2*>(dst), n, units, status);
+    } else {
+        hipLaunchKernelGGL(gather_rows_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, src, src_rows, idx, dst, n, units, status);
+    }
+    return ynet_check_launch("gather_rows");
 }
 
 }  // extern "C"

@@ -4,7 +4,8 @@ optimizer, log lines and checkpoint format).
 Reference: __init__ 46-75, _train 80-293 (freeze table 116-195), _test 299-352, forward_test / _forward_test /
 _forward_batch 354-516, prepare_data 518-584, load_params / save_params / load_separated_params 586-614,
 mark_*_bias_trainable 20-42.  ``saliency`` (new) wraps forward_test(decision='loss') and one backward; ``predict`` (new) forecasts
-from the observed steps alone: all K samples, scored and ranked (utils/predict.py).
+from the observed steps alone: all K samples, scored and ranked (utils/predict.py); ``load_styles`` / ``predict_styles`` (new) do so for
+agents of several styles at once (models/style_bank.py).
 Differences, all outside the arithmetic: image files are not decoded here (cv2/smp are out of scope) —
 ``prepare_data`` takes a dict {scene_id: float tensor [C,H,W]} in place of an image directory; an
 optional ``dp`` (dist.DataParallel) shards batches over the GPUs of a node.
@@ -323,9 +324,9 @@ class YNetTrainer:
 
     def _predict(self, df_obs, image_path, dataset_name, resize_factor, obs_len, waypoints, n_goal, n_traj, temperature,
                  batch_size=None, rel_threshold=0.002, use_TTST=False, use_CWS=False, CWS_params=None, use_raw_data=False,
-                 network=None, swap_semantic=False, return_maps=False, **kwargs):
+                 network=None, swap_semantic=False, return_maps=False, bank=None, style_column=None, **kwargs):
         import pandas as pd
-        from ..utils.predict import MAX_SAMPLES, predict
+        from ..utils.predict import MAX_SAMPLES, predict, predict_styles
         if dataset_name.lower() == "eth":
             raise NotImplementedError("predict: ETH/UCY forecasts are in world coordinates (homographies read from data files): "
                                       "out of the MI355X hot path, as in prepare_data")
@@ -359,15 +360,44 @@ class YNetTrainer:
         input_template = self.templates()
         results, frames = {}, []
         for observed, meta, scene_id in loader:
-            res = predict(model, images[scene_id], observed, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
-                          use_TTST=use_TTST, use_CWS=use_CWS, rel_thresh=rel_threshold, CWS_params=CWS_params, network=network,
-                          swap_semantic=swap_semantic, batch_size=batch_size, return_maps=return_maps)
+            kw = dict(use_TTST=use_TTST, use_CWS=use_CWS, rel_thresh=rel_threshold, CWS_params=CWS_params, network=network,
+                      swap_semantic=swap_semantic, batch_size=batch_size, return_maps=return_maps)
+            if bank is None:
+                res = predict(model, images[scene_id], observed, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature, **kw)
+            else:
+                styles = meta[0][style_column].to_numpy().reshape(-1, obs_len)
+                if (styles != styles[:, :1]).any():
+                    raise ValueError(f"predict_styles: scene {scene_id}: column {style_column!r} changes inside a track (one style per metaId)")
+                res = predict_styles(bank, images[scene_id], observed, styles[:, 0].tolist(), input_template, waypoints, n_goal, n_traj, obs_len,
+                                     resize_factor, temperature, **kw)
             results[scene_id] = res
             scores = res["scores"].cpu().numpy()
             n, k = scores.shape
             frames.append(pd.DataFrame({"metaId": np.repeat(meta[0].metaId.unique(), k), "sceneId": [scene_id] * (n * k),
                                         "rank": np.tile(np.arange(k), n), "score": scores.reshape(-1)}))
         return results, pd.concat(frames, ignore_index=True)
+
+    def load_styles(self, pretrained_path, styles):
+        """Load the base weights and keep one adapter set per style BESIDE the model (models/style_bank.py): ``styles`` maps a style
+        name to the path of a file written by save_params (or to a tuned state dict).  -> the StyleBank, also kept as ``self.styles``.
+        Unlike load_separated_params no tuned tensor is written into the model: style_bank.BASE_STYLE names the model as loaded."""
+        from .style_bank import StyleBank
+        self.load_params(pretrained_path)
+        self.styles = StyleBank(self.model.to(self.device), styles)
+        return self.styles
+
+    def predict_styles(self, df_obs, image_path_or_images, style_column="style", return_maps=False):
+        """predict() for scenes whose agents wear different styles of ``self.styles`` (load_styles): ``df_obs`` as for predict() (the
+        DataFrame form) with one more column, ``style_column``, that holds the style name of every row's agent (constant per metaId).
+        -> as predict(); every scene's dict carries ``style_index`` (utils.predict.predict_styles)."""
+        bank = getattr(self, "styles", None)
+        if bank is None:
+            raise RuntimeError("predict_styles: no style bank; call load_styles(pretrained_path, {name: tuned_path}) first")
+        if isinstance(df_obs, dict) or style_column not in df_obs.columns:
+            raise ValueError(f"predict_styles: df_obs must be a DataFrame with a {style_column!r} column (the style of every agent)")
+        for name in df_obs[style_column].unique():
+            bank.index(name)      # (an unknown style is refused before any scene runs)
+        return self._predict(df_obs, image_path_or_images, return_maps=return_maps, bank=bank, style_column=style_column, **self.params)
 
     # ------------------------------------------------------------------------------------------
     def forward_test(self, df_test, image_path, set_input, noisy_std_frac):

@@ -2762,6 +2762,109 @@ def score_rank_samples(prob: torch.Tensor, waypoint_samples: torch.Tensor, trajs
     return ranked, ranked_goals, score, order
 
 
+
+def _row_index(idx, dev, what: str):
+    """A row index as the kernels read it (device int32, contiguous) and, when it came from the host, its int64 NumPy copy (else None)."""
+    if torch.is_tensor(idx) and idx.is_cuda:
+        if idx.dtype != torch.int32 or idx.dim() != 1:
+            raise TypeError(f"{what}: a device index must be a 1-d int32 tensor, got {idx.dtype} {tuple(idx.shape)}")
+        return idx.contiguous(), None
+    host = np.asarray(idx.cpu() if torch.is_tensor(idx) else idx)
+    if host.ndim != 1 or host.size == 0 or not np.issubdtype(host.dtype, np.integer):
+        raise ValueError(f"{what}: expected a non-empty 1-d array of integers, got {host.dtype} {host.shape}")
+    host = host.astype(np.int64)
+    if dev is None:
+        return None, host
+    return torch.from_numpy(host.astype(np.int32)).to(dev), host
+
+
+def check_row_permutation(out_row, B: int):
+    """Raise unless the host array ``out_row`` holds every row 0 .. B - 1 exactly once (score_rank_samples_rows: two agents naming
+    one output row would race, a row named by none would stay unwritten)."""
+    _, host = _row_index(out_row, None, "score_rank_samples_rows out_row")
+    if host.shape[0] != B or not np.array_equal(np.sort(host), np.arange(B)):
+        raise ValueError(f"score_rank_samples_rows: out_row must be a permutation of 0 .. {B - 1} (one output row per agent), got "
+                         f"{host.tolist() if host.size <= 16 else str(host[:16].tolist()) + ' ...'}")
+
+
+def score_rank_samples_rows(prob: torch.Tensor, waypoint_samples: torch.Tensor, trajs: torch.Tensor, resize_factor: float, out_row):
+    """score_rank_samples for a batch that was reordered before the sweep (ynet_score_rank_samples_rows; utils/predict.py:
+    predict_styles sorts the agents by style): agent b of the batch writes its ranked trajectories, way-points, scores and order at
+    row out_row[b] of the results, so they come back in the caller's order from the ranking launch itself.  out_row: a permutation of
+    0 .. B - 1, as a host array / list (checked here) or a device int32 tensor (checked by the kernel: an entry out of range writes
+    nothing and raises).  Operands, rules and results otherwise as score_rank_samples."""
+    for t, what in ((prob, "prob"), (waypoint_samples, "waypoint_samples"), (trajs, "trajs")):
+        _need_gpu(t, "score_rank_samples_rows " + what)
+    if prob.dim() != 4 or waypoint_samples.dim() != 4 or trajs.dim() != 4:
+        raise ValueError("score_rank_samples_rows: expected prob [B, n_wp, H, W], waypoint_samples [K, B, n_wp, 2] and trajs [K, B, pred_len, 2]")
+    B, n_wp, H, W = prob.shape
+    K, pred_len = waypoint_samples.shape[0], trajs.shape[2]
+    if tuple(waypoint_samples.shape) != (K, B, n_wp, 2) or tuple(trajs.shape) != (K, B, pred_len, 2):
+        raise ValueError(f"score_rank_samples_rows: waypoint_samples {tuple(waypoint_samples.shape)} / trajs {tuple(trajs.shape)} do not go "
+                         f"with prob {tuple(prob.shape)} (expected [K, {B}, {n_wp}, 2] and [K, {B}, pred_len, 2])")
+    for t, what in ((prob, "prob"), (waypoint_samples, "waypoint_samples"), (trajs, "trajs")):
+        if not t.is_contiguous():
+            raise ValueError(f"score_rank_samples_rows: {what} is not contiguous (strides {t.stride()}); the kernel addresses dense arrays")
+    if not float(resize_factor) > 0:
+        raise ValueError("score_rank_samples_rows: the resize factor must be positive")
+    dev = prob.device
+    if not (torch.is_tensor(out_row) and out_row.is_cuda):
+        check_row_permutation(out_row, B)
+    rows, _ = _row_index(out_row, dev, "score_rank_samples_rows out_row")
+    if rows.numel() != B:
+        raise ValueError(f"score_rank_samples_rows: out_row holds {rows.numel()} entries for {B} agents")
+    with torch.no_grad():
+        prob, waypoint_samples, trajs = prob.detach(), waypoint_samples.detach(), trajs.detach()
+        ranked = torch.empty((B, K, pred_len, 2), device=dev, dtype=torch.float32)
+        ranked_goals = torch.empty((B, K, n_wp, 2), device=dev, dtype=torch.float32)
+        score = torch.empty((B, K), device=dev, dtype=torch.float32)
+        order = torch.empty((B, K), device=dev, dtype=torch.int32)
+        st = _status_flag(_score_status, dev)
+        inv = float(np.float32(1.0 / float(resize_factor)))      # (as score_rank_samples)
+        lib = _lib()
+        L.check(lib.ynet_score_rank_samples_rows(prob.data_ptr(), waypoint_samples.data_ptr(), trajs.data_ptr(), rows.data_ptr(), B, K, n_wp,
+                                                 pred_len, H, W, inv, score.data_ptr(), order.data_ptr(), ranked.data_ptr(),
+                                                 ranked_goals.data_ptr(), st.data_ptr(), _stream()), lib)
+        code = int(st.item())
+        if code != 0:
+            st.zero_()
+            raise RuntimeError(f"score_rank_samples_rows: a sample lies outside the {H}x{W} map" if code == 1 else
+                               f"score_rank_samples_rows: out_row names a row outside 0 .. {B - 1}")
+    return ranked, ranked_goals, score, order
+
+
+_gather_status = {}
+
+
+def gather_rows(src: torch.Tensor, idx) -> torch.Tensor:
+    """dst[i] = src[idx[i]] along the first dimension of a contiguous fp32 tensor (ynet_gather_rows): how predict_styles builds its
+    style-sorted batch.  idx: host array / list of row numbers (checked here) or a device int32 tensor (an entry out of range is
+    reported by check_gather_status()).  Indices may repeat.  -> [len(idx), *src.shape[1:]]"""
+    _need_gpu(src, "gather_rows")
+    if src.dim() < 1 or src.shape[0] == 0 or src[0].numel() == 0:
+        raise ValueError(f"gather_rows: nothing to gather from a tensor of shape {tuple(src.shape)}")
+    if not src.is_contiguous():
+        raise ValueError(f"gather_rows: the source is not contiguous (strides {src.stride()}); the kernel addresses dense rows")
+    rows, host = _row_index(idx, src.device, "gather_rows idx")
+    if host is not None and (host.min() < 0 or host.max() >= src.shape[0]):
+        raise ValueError(f"gather_rows: an index lies outside 0 .. {src.shape[0] - 1}")
+    n, row_floats = rows.numel(), src[0].numel()
+    dst = torch.empty((n,) + tuple(src.shape[1:]), device=src.device, dtype=torch.float32)
+    st = _status_flag(_gather_status, src.device)
+    lib = _lib()
+    L.check(lib.ynet_gather_rows(src.detach().data_ptr(), src.shape[0], rows.data_ptr(), dst.data_ptr(), n, row_floats, st.data_ptr(),
+                                 _stream()), lib)
+    return dst
+
+
+def check_gather_status():
+    """Raise if a gather_rows call met a device-side index outside its source (checked at a sync point)."""
+    for dev, st in _gather_status.items():
+        if int(st.item()) != 0:
+            st.zero_()
+            raise RuntimeError("gather_rows: an index lies outside the source")
+
+
 def check_patch_status():
     """Raise if a device-side coordinate ever left the template (checked at sync points)."""
     for dev, st in _patch_status.items():

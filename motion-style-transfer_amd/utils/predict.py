@@ -9,6 +9,9 @@ way-point draws with optional TTST and CWS, the K folded trajectory-decoder pass
 back by descending score.  Every draw takes its seed from torch's CPU generator (NumPy's for the TTST centres) in evaluate()'s
 order, so under torch.manual_seed(s) predict() on the first obs_len steps of a batch takes exactly the draws evaluate() takes on
 that batch.  Nothing is captured into a hipGraph here; evaluate()'s captured-sweep cache is not touched.
+
+``predict_styles`` is predict() for a scene whose agents wear different styles: one frozen model, the adapter sets of a
+models.style_bank.StyleBank, one call.
 """
 import numpy as np
 import torch
@@ -28,6 +31,24 @@ def _observed_tensor(observed, obs_len):
         raise ValueError(f"predict: observed holds {obs.shape[1]} steps per agent, obs_len is {obs_len}: pass exactly the observed steps "
                          f"(a longer track is never cut silently)")
     return obs.float()
+
+
+def _draw_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, n_goal, n_traj, obs_len, use_TTST, use_CWS, rel_thresh, CWS_params,
+                    device):
+    """The goal / way-point draws of one chunk, in evaluate()'s order (utils/evaluate.py:109-224) -> [K, n, n_wp, 2]"""
+    n_wp = len(waypoints)
+    if use_TTST:
+        goal_samples = ttst_goals(model, wp_sigmoid[:, -1:], pred_goal_map[:, waypoints[-1:]], n_goal, rel_thresh)
+    else:
+        goal_samples = sampling(wp_sigmoid[:, -1:], num_samples=n_goal).permute(2, 0, 1, 3)
+    if use_CWS and n_wp > 1:
+        last_observed = batch[:, obs_len - 1].to(device)
+        return cws_waypoints(model, wp_sigmoid, goal_samples, last_observed, n_goal, n_traj,
+                             CWS_params["sigma_factor"], CWS_params["ratio"], CWS_params["rot"])
+    if n_wp > 1:
+        waypoint_samples = sampling(wp_sigmoid[:, :-1], num_samples=n_goal * n_traj).permute(2, 0, 1, 3)
+        return torch.cat([waypoint_samples, goal_samples.repeat(n_traj, 1, 1, 1)], dim=2)
+    return goal_samples
 
 
 def predict(model, scene_image, observed, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
@@ -99,19 +120,8 @@ def predict(model, scene_image, observed, input_template, waypoints, n_goal, n_t
                     if tuple(waypoint_samples.shape) != (K, n, n_wp, 2):
                         raise ValueError(f"predict: forced samples {tuple(waypoint_samples.shape)} for the chunk at {b}, expected {(K, n, n_wp, 2)}")
                 else:
-                    if use_TTST:
-                        goal_samples = ttst_goals(model, wp_sigmoid[:, -1:], pred_goal_map[:, waypoints[-1:]], n_goal, rel_thresh)
-                    else:
-                        goal_samples = sampling(wp_sigmoid[:, -1:], num_samples=n_goal).permute(2, 0, 1, 3)
-                    if use_CWS and n_wp > 1:
-                        last_observed = batch[:, obs_len - 1].to(device)
-                        waypoint_samples = cws_waypoints(model, wp_sigmoid, goal_samples, last_observed, n_goal, n_traj,
-                                                         CWS_params["sigma_factor"], CWS_params["ratio"], CWS_params["rot"])
-                    elif n_wp > 1:
-                        waypoint_samples = sampling(wp_sigmoid[:, :-1], num_samples=n_goal * n_traj).permute(2, 0, 1, 3)
-                        waypoint_samples = torch.cat([waypoint_samples, goal_samples.repeat(n_traj, 1, 1, 1)], dim=2)
-                    else:
-                        waypoint_samples = goal_samples
+                    waypoint_samples = _draw_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, n_goal, n_traj, obs_len, use_TTST,
+                                                       use_CWS, rel_thresh, CWS_params, device)
                 waypoint_samples = waypoint_samples.float().contiguous()
 
                 if return_maps:
@@ -129,3 +139,126 @@ def predict(model, scene_image, observed, input_template, waypoints, n_goal, n_t
     finally:
         model.train(was_training)
     return {k: (v[0] if len(v) == 1 else torch.cat(v)) for k, v in out.items()}
+
+
+def predict_styles(bank, scene_image, observed, style, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
+                   use_TTST=False, use_CWS=False, rel_thresh=0.002, CWS_params=None, network=None, swap_semantic=False, batch_size=None,
+                   max_effective_batch=256, forced_samples=None, return_maps=False):
+    """predict() over the agents of ONE scene that wear different styles of a StyleBank: the adapted encoder convolutions run once
+    per style on that style's rows, every other layer and all K decoder passes once over the whole batch.
+
+    bank             models.style_bank.StyleBank (holds the model)
+    style            [N] style names or indices, one per agent (bank.names / bank.index; style_bank.BASE_STYLE = the model as loaded)
+    forced_samples   as for predict(), in the CALLER's order: {first agent of a chunk: [K, n, n_wp, 2]} or one tensor [K, N, n_wp, 2]
+    every other argument and every result as for predict(); the results are in the caller's order and carry ``style_index`` [N] (int64).
+
+    Each chunk (``batch_size`` agents of the caller's order; it may hold any subset of the styles) is stable-sorted by style index on
+    the host -- the labels are host data.  ynet_gather_rows builds the sorted observed coordinates and forced samples, and
+    ynet_score_rank_samples_rows writes every agent's ranked results at its row of the caller's order.  Without forced samples the
+    draws are taken over the SORTED chunk: draw row j belongs to the j-th agent of the sorted order, so a mixed batch does not take
+    the draws predict() would take for the caller's order.  When a chunk holds one style the sort is the identity, nothing is
+    gathered and the launches are predict()'s on a model carrying that style.  With ``return_maps`` the maps are computed in sorted
+    order and gathered back into the caller's order (one ynet_gather_rows pass over each map, paid only when the maps are asked for).
+    evaluate()'s captured-sweep cache is neither used nor touched; the model's filter caches are not written (StyleBank)."""
+    from ..models.style_bank import sort_by_style
+    model = bank.model
+    waypoints = list(waypoints)
+    n_wp = len(waypoints)
+    n_goal, n_traj, obs_len = int(n_goal), int(n_traj), int(obs_len)
+    K = n_goal * n_traj
+    if n_goal < 1 or n_traj < 1:
+        raise ValueError(f"predict_styles: n_goal = {n_goal}, n_traj = {n_traj}: at least one sample per agent is needed")
+    if K > MAX_SAMPLES:
+        raise ValueError(f"predict_styles: n_goal * n_traj = {K} samples per agent; the ranking kernel takes up to {MAX_SAMPLES}")
+    if n_wp < 1:
+        raise ValueError("predict_styles: no way-points")
+    if use_CWS and n_wp > 1 and CWS_params is None:
+        raise ValueError("predict_styles: use_CWS needs CWS_params (sigma_factor, ratio, rot)")
+    if not float(resize_factor) > 0:
+        raise ValueError("predict_styles: resize_factor must be positive")
+    if batch_size is not None and int(batch_size) < 1:
+        raise ValueError("predict_styles: batch_size must be positive")
+    obs = _observed_tensor(observed, obs_len)
+    if not torch.is_tensor(scene_image) or scene_image.dim() != 3:
+        raise ValueError("predict_styles: scene_image must be the tensor [C, H, W] of one scene")
+    N = obs.shape[0]
+    if N == 0:
+        raise ValueError("predict_styles: no agents (observed is empty)")
+    style_index = np.asarray(bank.indices(style), dtype=np.int64)      # (an unknown style is refused here)
+    if style_index.shape != (N,):
+        raise ValueError(f"predict_styles: {style_index.size} styles for {N} agents: one name or index per agent is needed")
+    if torch.is_tensor(forced_samples) and tuple(forced_samples.shape) != (K, N, n_wp, 2):
+        raise ValueError(f"predict_styles: forced_samples {tuple(forced_samples.shape)}, expected {(K, N, n_wp, 2)} in the caller's order")
+    step = N if batch_size is None else int(batch_size)
+    device = next(model.parameters()).device
+    was_training = model.training
+    model.eval()
+    out = {k: [] for k in ["trajectories", "waypoints", "scores", "order"] + (["goal_map", "goal_sigmoid_map"] if return_maps else [])}
+    try:
+        with torch.no_grad():
+            # ops.refresh_filters for the shadows and the shared layers, on the caller's stream, before the decoder passes fan out over two
+            bank.refresh()
+            scene = model.segmentation(scene_image.to(device).unsqueeze(0))
+            scene = model.adapt_semantic(scene)
+            if swap_semantic:
+                scene = swap_pavement_terrain(scene)
+            if network == "embed":
+                scene = model.scene_embedding(scene)
+            _, _, H, W = scene.shape
+            for b in range(0, N, step):
+                batch = obs[b:b + step]
+                n = len(batch)
+                perm, offsets = sort_by_style(style_index[b:b + n], len(bank))
+                mixed = not np.array_equal(perm, np.arange(n))
+                if mixed:
+                    perm_dev = torch.from_numpy(perm.astype(np.int32)).to(device)
+                    batch = ops.gather_rows(batch.to(device).contiguous(), perm_dev)
+                observed_map = gather_patches(input_template, batch.reshape(-1, 2), H, W).view(-1, obs_len, H, W)
+                if network == "embed":
+                    observed_map = model.motion_embedding(observed_map)
+                features = bank.pred_features(scene.expand(n, -1, -1, -1), observed_map, offsets)
+                pred_goal_map = model.pred_goal(features)
+                wp_sigmoid = ops.sigmoid_temp(pred_goal_map, waypoints, temperature)
+
+                if forced_samples is not None:
+                    forced = forced_samples[:, b:b + n] if torch.is_tensor(forced_samples) else forced_samples[b]
+                    waypoint_samples = forced.to(device)
+                    if tuple(waypoint_samples.shape) != (K, n, n_wp, 2):
+                        raise ValueError(f"predict_styles: forced samples {tuple(waypoint_samples.shape)} for the chunk at {b}, expected {(K, n, n_wp, 2)}")
+                    waypoint_samples = waypoint_samples.float().contiguous()
+                    if mixed:      # a row gather inside each of the K slabs
+                        slab_rows = (torch.arange(K, device=device, dtype=torch.int32)[:, None] * n + perm_dev[None]).reshape(-1)
+                        waypoint_samples = ops.gather_rows(waypoint_samples.view(K * n, n_wp, 2), slab_rows).view(K, n, n_wp, 2)
+                else:
+                    waypoint_samples = _draw_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, n_goal, n_traj, obs_len, use_TTST,
+                                                       use_CWS, rel_thresh, CWS_params, device)
+                waypoint_samples = waypoint_samples.float().contiguous()
+
+                if return_maps:
+                    sig_map = model.sigmoid(pred_goal_map / temperature)
+                    if mixed:
+                        back = torch.from_numpy(np.argsort(perm).astype(np.int32)).to(device)      # caller row i <- sorted row back[i]
+                        out["goal_map"].append(ops.gather_rows(pred_goal_map.contiguous(), back))
+                        out["goal_sigmoid_map"].append(ops.gather_rows(sig_map.contiguous(), back))
+                    else:
+                        out["goal_map"].append(pred_goal_map)
+                        out["goal_sigmoid_map"].append(sig_map)
+
+                trajs_samples = _decoder_passes(model, features, waypoint_samples, input_template, n, n_wp, H, W, max_effective_batch, device)
+                if mixed:
+                    ranked, ranked_goals, score, order = ops.score_rank_samples_rows(wp_sigmoid, waypoint_samples, trajs_samples.contiguous(),
+                                                                                    resize_factor, perm)
+                else:
+                    ranked, ranked_goals, score, order = ops.score_rank_samples(wp_sigmoid, waypoint_samples, trajs_samples.contiguous(),
+                                                                               resize_factor)
+                out["trajectories"].append(ranked)
+                out["waypoints"].append(ranked_goals)
+                out["scores"].append(score)
+                out["order"].append(order)
+                ops.check_patch_status()      # (the ranking call waited for the chunk)
+                ops.check_gather_status()
+    finally:
+        model.train(was_training)
+    res = {k: (v[0] if len(v) == 1 else torch.cat(v)) for k, v in out.items()}
+    res["style_index"] = torch.from_numpy(style_index).to(device)
+    return res
