@@ -239,9 +239,11 @@ int ynet_upsample2x_conv2d_winograd(const float* src, long long src_bs, const fl
  *   filter cache `cache`: 16-byte aligned device memory of ynet_conv2d_auto_cache_floats(desc) floats (0: this call needs none);
  *                `cache_tag`: two 64-bit words in HOST memory, zero before the first call; `wp_version`: any number the caller changes
  *                whenever the contents of wp change.  The transforms run on `stream` when the tag does not match (first call, new
- *                version, or a plan that differs: another batch / raster size can choose another family); a cache belongs to ONE
- *                (layer, direction) and one stream order -- a caller that shares it between streams orders them itself (taken->transformed
- *                tells when a transform was enqueued).
+ *                version, or a plan that differs: another batch / raster size can choose another family and then OVERWRITES the cache,
+ *                even when both plans need the same number of floats); a cache belongs to ONE (layer, direction) and one stream order
+ *                -- a caller that shares it between streams orders them itself (taken->transformed tells when a transform was
+ *                enqueued).  A caller that captures graphs -- a replay reads the cache and never transforms -- or that alternates
+ *                batch / raster sizes keeps ONE cache (buffer and tag) PER LAYOUT: ynet_conv2d_auto_cache_layout(desc) names it.
  *   flags        YNET_AUTO_* below: development switches that restrict the choice (results then differ by fp32 rounding only); YNET_AUTO_UPCONV_BWD
  *                selects another operation instead (an up-convolution's data gradient at the low resolution, see ynet_upconv_dgrad_ring).
  *   taken        (optional) what ran: the family, the launches with the template arguments their rocprofv3 kernel names carry, whether
@@ -306,6 +308,11 @@ typedef struct YnetConvTaken {
     int wrote_s2d;         /* bit i: destination i was written space-to-depth */
 } YnetConvTaken;
 long long ynet_conv2d_auto_cache_floats(const YnetConvAuto* desc);
+/* The layout of the filter cache this descriptor's plan uses: the value ynet_conv2d_auto stores in cache_tag[0].  0: the call keeps no
+ * transformed filter.  Two descriptors with the same value (and the same wp) can share a cache; two with different values cannot, even
+ * when they need the same number of floats.  *floats (optional) receives ynet_conv2d_auto_cache_floats(desc).  A descriptor no kernel
+ * serves (or NULL): 0 with *floats = -1, the reason in ynet_last_error().  Host code only: nothing is launched. */
+unsigned long long ynet_conv2d_auto_cache_layout(const YnetConvAuto* desc, long long* floats);
 long long ynet_conv2d_auto_workspace_floats(const YnetConvAuto* desc);
 int ynet_conv2d_auto(const YnetConvAuto* desc, YnetConvTaken* taken, void* stream);
 /* The choice ynet_conv2d_auto WOULD make for this descriptor (family, variant, number of launches), without launching anything: pointers are
@@ -327,7 +334,7 @@ int ynet_conv2d_auto_plan(const YnetConvAuto* desc, YnetConvTaken* taken);
  * layer's RAW filter K [cout][cin][3][3] (not packed), H x W = h x w (the low resolution), K = 3, relu_of optional (dx is then written through that activation's
  * ReLU backward: relu_of > 0 ? dx : 0, ring included), nothing else (no bias, relu, mask, upsample2x, pooled, addend, bit masks, dst_s2d: refused).  The cache
  * (ynet_conv2d_auto_cache_floats of the same descriptor) receives Keff, the 16 tables and the transforms of Keff the plan takes, all made when cache_tag /
- * wp_version do not match (taken->transformed); give this form a cache of its own (one layer, one plan).  taken: the low-resolution data gradient's family /
+ * wp_version do not match (taken->transformed); give this form a cache of its own (one layer, one ynet_conv2d_auto_cache_layout value).  taken: the low-resolution data gradient's family /
  * variant, nlaunch with the ring launch counted; ynet_conv2d_auto_plan answers the same without launching.
  *
  * THE PIECES: ynet_upconv_tables writes, from K, Keff in the layout of ynet_pack_weight(Keff, 4 cout, cin, 3, mode 1) ([rows][9][cols], rows = 4 cout padded to

@@ -89,6 +89,7 @@ SIGNATURES = {
     "ynet_winograd16_filter": (c_i, [c_fp, c_fp, PI, c_i, c_i, c_i, c_i, c_fp]),
     "ynet_conv2d_winograd16": (c_i, [PP, PI, PLL, c_i, c_fp, c_fp, c_fp, c_ll, c_i, c_i, c_i, c_i, c_i, c_fp, c_ll, c_fp, c_ll, c_i, c_fp, c_ll, c_fp]),
     "ynet_conv2d_auto_cache_floats": (c_ll, [ctypes.POINTER(ConvAuto)]),
+    "ynet_conv2d_auto_cache_layout": (ctypes.c_ulonglong, [ctypes.POINTER(ConvAuto), ctypes.POINTER(c_ll)]),
     "ynet_conv2d_auto_workspace_floats": (c_ll, [ctypes.POINTER(ConvAuto)]),
     "ynet_conv2d_auto": (c_i, [ctypes.POINTER(ConvAuto), ctypes.POINTER(ConvTaken), c_fp]),
     "ynet_conv2d_auto_plan": (c_i, [ctypes.POINTER(ConvAuto), ctypes.POINTER(ConvTaken)]),

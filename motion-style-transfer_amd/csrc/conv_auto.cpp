@@ -343,6 +343,7 @@ struct UpPlan {
 };
 
 int make_up_plan(const YnetConvAuto* a, UpPlan& u);
+unsigned long long up_signature(const UpPlan& u);
 int run_upconv_bwd(const YnetConvAuto* a, YnetConvTaken* taken, void* stream);
 int run_plan(const YnetConvAuto* a, const Plan& p, YnetConvTaken t, YnetConvTaken* taken, void* stream);
 
@@ -358,6 +359,20 @@ long long ynet_conv2d_auto_cache_floats(const YnetConvAuto* a) {
     Plan p;
     if (!a || make_plan(a, p)) return -1;
     return p.cache_floats;
+}
+
+unsigned long long ynet_conv2d_auto_cache_layout(const YnetConvAuto* a, long long* floats) {
+    long long need = -1;
+    unsigned long long layout = 0;
+    if (a && (a->flags & YNET_AUTO_UPCONV_BWD)) {
+        UpPlan u;
+        if (!make_up_plan(a, u)) { need = u.cache_floats; layout = up_signature(u); }
+    } else if (a) {
+        Plan p;
+        if (!make_plan(a, p)) { need = p.cache_floats; layout = p.nl ? signature(p) : 0; }
+    }
+    if (floats) *floats = need;
+    return layout;
 }
 
 long long ynet_conv2d_auto_workspace_floats(const YnetConvAuto* a) {
@@ -611,6 +626,16 @@ int make_up_plan(const YnetConvAuto* a, UpPlan& u) {
     return 0;
 }
 
+// the layout of an up-convolution backward's cache: the inner plan's signature, mixed with the form and the filter's shape
+unsigned long long up_signature(const UpPlan& u) {
+    unsigned long long sig = signature(u.p);
+    for (long long v : {0x7570636f6e76ll, (long long)u.cout, (long long)u.cin}) {
+        sig ^= (unsigned long long)v;
+        sig *= 1099511628211ull;
+    }
+    return sig ? sig : 1;
+}
+
 int run_upconv_bwd(const YnetConvAuto* a, YnetConvTaken* taken, void* stream) {
     UpPlan u;
     if (int rc = make_up_plan(a, u)) return rc;
@@ -622,12 +647,7 @@ int run_upconv_bwd(const YnetConvAuto* a, YnetConvTaken* taken, void* stream) {
     memset(&t, 0, sizeof(t));
     t.family = u.p.family;
     t.variant = u.p.variant;
-    unsigned long long sig = signature(u.p);
-    for (long long v : {0x7570636f6e76ll, (long long)u.cout, (long long)u.cin}) {
-        sig ^= (unsigned long long)v;
-        sig *= 1099511628211ull;
-    }
-    sig = sig ? sig : 1;
+    const unsigned long long sig = up_signature(u);
     if (a->cache_tag[0] != sig || a->cache_tag[1] != a->wp_version) {
         if (int rc = ynet_upconv_tables(a->wp, u.cout, u.cin, a->cache, a->cache + u.tab_off, stream)) return rc;
         if (int rc = transform(&u.in, u.p, stream)) return rc;

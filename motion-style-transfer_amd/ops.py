@@ -356,25 +356,12 @@ _wino_cat_eval = True        # the concatenated-source / shared-term launches
 _wino_plain_eval = True      # the one-source launches
 
 
-def _wino_made(entry):
-    """A Winograd filter entry just made on the current stream: remembers that stream and an event behind the transform launch."""
-    if not torch.cuda.is_available() or torch.cuda.is_current_stream_capturing():
-        return entry + (None, None)
-    ev = torch.cuda.Event()
-    ev.record()
-    return entry + (torch.cuda.current_stream().cuda_stream, ev)
-
-
-def _wino_ready(entry):
-    """Filters are transformed lazily at a layer's first Winograd launch -- possibly on one of evaluate()'s two sweep streams, with the
-    other stream's cache hit a few microseconds behind and no dependency on the transform: a hit from another stream waits for the
-    maker's event until that has completed (the first call of a process only; never inside a capture, which follows an eager pass)."""
-    stream, ev = entry[-2], entry[-1]
-    if ev is not None and not torch.cuda.is_current_stream_capturing():
-        cur = torch.cuda.current_stream()
-        if cur.cuda_stream != stream and not ev.query():
-            cur.wait_event(ev)
-    return entry
+def _count_launches(n, slice_form=False):
+    """wino_stats for n Winograd launches.  (conv2d_auto_raw and upconv_dgrad_raw keep their own bump, as they keep their own workspace lookup and filter entry:
+    both functions are left as they were until their cache is keyed by ynet_conv2d_auto_cache_layout.)"""
+    wino_stats["launches"] += n
+    if slice_form:
+        wino_stats["launches16"] = wino_stats.get("launches16", 0) + n
 
 
 def winograd_filter(wp: torch.Tensor, cin: int, cout: int, col0: int = 0, cols_total: int = None) -> torch.Tensor:
@@ -492,30 +479,43 @@ def _wino16_supported(srcs_c, cout, B, H, W, K=3):
     return bool(_lib().ynet_conv2d_winograd16_supported(B, H, W, (ctypes.c_int * len(srcs_c))(*srcs_c), len(srcs_c), cout, K))
 
 
-def _wino16_filter(wino, wp, row0, cs, cout, col0, ctot):
-    """The slice-major Winograd filter (ynet_winograd16_filter) of output channels [col0, col0 + cout) of the packed filter wp for sources of
-    cs channels each, from the filter's input-channel row row0 on; kept in the layer's cache."""
-    lib = _lib()
+def _wino_filter(wino, kind, wp, row0, cs, cout, col0, ctot, make=True):
+    """The transformed filter (a _Filter; `.u` is the tensor) of output channels [col0, col0 + cout) of the packed filter wp (ctot output channels in all) for
+    sources of cs channels each, from the filter's input-channel row row0 on, kept in the layer's cache wino = (dict, "fwd" | "dgrad" | "rest").  kind: "wino"
+    ynet_winograd_filter (one source), "cat" ynet_winograd_filter_cat, "wino16" ynet_winograd16_filter -- csrc/conv_auto.cpp's `Launch`, and like its
+    signature the key names all of it.  make=False: None where the entry was not made before."""
     cache, what = wino
-    key = "wino16_%s_%d_%d_%d" % (what, row0, col0, cout)
-    ent = cache.get(key)
-    if ent is None or ent[0] is not wp or ent[2] != cs:
+    cs = tuple(int(c) for c in cs)
+
+    def transform():
+        lib = _lib()
         ca = (ctypes.c_int * len(cs))(*cs)
-        u = torch.empty(lib.ynet_winograd16_filter_floats(ca, len(cs), cout), device=wp.device, dtype=torch.float32)
-        cols_pad = -(-ctot // 64) * 64
-        L.check(lib.ynet_winograd16_filter(wp.data_ptr() + 4 * row0 * 9 * cols_pad, u.data_ptr(), ca, len(cs), cout, col0, ctot, _stream()), lib)
-        ent = cache[key] = _wino_made((wp, u, cs))
-    _wino_ready(ent)
-    return ent
+        src = wp.data_ptr() + 4 * row0 * 9 * (-(-ctot // 64) * 64)
+        if kind == "wino":
+            u = torch.empty(lib.ynet_winograd_filter_floats(cs[0], cout), device=wp.device, dtype=torch.float32)
+            rc = lib.ynet_winograd_filter(src, u.data_ptr(), cs[0], cout, col0, ctot, _stream())
+        elif kind == "cat":
+            u = torch.empty(lib.ynet_winograd_filter_cat_floats(ca, len(cs), cout), device=wp.device, dtype=torch.float32)
+            rc = lib.ynet_winograd_filter_cat(src, u.data_ptr(), ca, len(cs), cout, col0, ctot, _stream())
+        else:
+            u = torch.empty(lib.ynet_winograd16_filter_floats(ca, len(cs), cout), device=wp.device, dtype=torch.float32)
+            rc = lib.ynet_winograd16_filter(src, u.data_ptr(), ca, len(cs), cout, col0, ctot, _stream())
+        L.check(rc, lib)
+        return u
+    return _filter(cache, (kind, what, row0, cs, col0, cout, ctot), wp, transform if make else None)
+
+
+def _wino16_filter(wino, wp, row0, cs, cout, col0, ctot):
+    """The slice-major Winograd filter (ynet_winograd16_filter), see _wino_filter."""
+    return _wino_filter(wino, "wino16", wp, row0, cs, cout, col0, ctot)
 
 
 def _wino16(wino, wp, row0, srcs, bias, dst, cout, col0, ctot, B, H, W, relu, relu_of=None, addend=None, pool=None):
     """One ynet_conv2d_winograd16 launch over output channels [col0, col0 + cout) of the packed filter wp (ctot output channels in all)
     and its input-channel rows from row0 on, the transformed filter kept in the layer's cache."""
-    ent = _wino16_filter(wino, wp, row0, tuple(s_[1] for s_ in srcs), cout, col0, ctot)
-    conv2d_winograd16_raw(srcs, ent[1], None if bias is None else bias[col0:col0 + cout], dst, cout, B, H, W, relu, relu_of=relu_of, addend=addend, pool=pool)
-    wino_stats["launches"] += 1
-    wino_stats["launches16"] = wino_stats.get("launches16", 0) + 1
+    u = _wino16_filter(wino, wp, row0, [s_[1] for s_ in srcs], cout, col0, ctot).u
+    conv2d_winograd16_raw(srcs, u, None if bias is None else bias[col0:col0 + cout], dst, cout, B, H, W, relu, relu_of=relu_of, addend=addend, pool=pool)
+    _count_launches(1, slice_form=True)
 
 
 def _pad4(c):
@@ -604,7 +604,7 @@ def conv2d_auto_raw(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=None, 
             if ent is None or ent[0] is not wp or ent[1].numel() < need:
                 ent = cache[key] = [wp, torch.empty(need, device=wp.device, dtype=torch.float32), (ctypes.c_ulonglong * 2)(0, 0), None, None]
             elif ent[4] is not None and not torch.cuda.is_current_stream_capturing():
-                # (made on another stream a few microseconds ago -- evaluate()'s two sweep streams: wait for the maker's event, as _wino_ready)
+                # (made on another stream a few microseconds ago -- evaluate()'s two sweep streams: wait for the maker's event, as _Filter.ready)
                 cur = torch.cuda.current_stream()
                 if cur.cuda_stream != ent[3] and not ent[4].query():
                     cur.wait_event(ent[4])
@@ -718,17 +718,10 @@ def _conv2d_raw_py(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=None, p
             cs = (ctypes.c_int * len(srcs))(*[s_[1] for s_ in srcs])
             if lib.ynet_conv2d_winograd_cat_supported(B, H, W, cs, len(srcs), 32, K):
                 # the encoder's conv + ReLU in front of a max-pool: the Winograd launch writes the pooled copy itself (a lane holds the block)
-                cache, what = wino
-                key = "wino_cat_" + what
-                ent = cache.get(key)
-                if ent is None or ent[0] is not wp or ent[2] != tuple(cs):
-                    u = torch.empty(lib.ynet_winograd_filter_cat_floats(cs, len(srcs), 32), device=wp.device, dtype=torch.float32)
-                    L.check(lib.ynet_winograd_filter_cat(wp.data_ptr(), u.data_ptr(), cs, len(srcs), 32, 0, 32, _stream()), lib)
-                    ent = cache[key] = _wino_made((wp, u, tuple(cs)))
-                _wino_ready(ent)
+                u = _wino_filter(wino, "cat", wp, 0, cs, 32, 0, 32).u
                 code = pool_code if (relu and _pool_code_allowed) else None
-                conv2d_winograd_cat_raw(srcs, ent[1], bias, (dsts[0][0], dsts[0][2]), B, H, W, relu, pool=pooled, pool_code=code)
-                wino_stats["launches"] += 1
+                conv2d_winograd_cat_raw(srcs, u, bias, (dsts[0][0], dsts[0][2]), B, H, W, relu, pool=pooled, pool_code=code)
+                _count_launches(1)
                 return "winograd_cat:2,6|code" if code is not None else "winograd_cat:2,3"
         if (wino is not None and K == 3 and dsts[0][0] % 8 == 0 and dsts[0][2] % 2 == 0 and all(len(s_) == 3 and s_[0] % 16 == 0 and s_[2] % 4 == 0 for s_ in srcs)
                 and _wino16_supported([s_[1] for s_ in srcs], dsts[0][1], B, H, W)):
@@ -769,22 +762,15 @@ def _conv2d_raw_py(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=None, p
                 and pieces[1][1] == 32 and piece_dst[1][1] and pieces[1][3] == pieces[0][3] + 16 and all(p_[0] % 8 == 0 and p_[2] % 2 == 0 for p_ in pieces)
                 and all(lib.ynet_conv2d_winograd_supported(B, H, W, cin, p_[1], K) for p_ in pieces) and lib.ynet_conv2d_winograd_split_supported(B, H, W, cin)):
             # [16, 32] channels of a plain data gradient (cat(up-sampled 16, skip 32[, way-point map]) at the decoders' last level): one launch, dy read once
-            cache, what = wino
-            col0 = pieces[0][3]
-            key = "wino_%s_%d_48" % (what, col0)
-            ent = cache.get(key)
-            if ent is None or ent[0] is not wp:
-                ent = cache[key] = _wino_made((wp, winograd_filter(wp, cin, 48, col0, ctot)))
-            _wino_ready(ent)
+            u = _wino_filter(wino, "wino", wp, 0, (cin,), 48, pieces[0][3], ctot).u
             s2d = bool(dst_s2d and dst_s2d[piece_dst[0][0]])
-            conv2d_winograd_split_raw((srcs[0][0], srcs[0][2]), ent[1], (pieces[0][0], pieces[0][2]), s2d, (pieces[1][0], pieces[1][2]), cin, B, H, W)
+            conv2d_winograd_split_raw((srcs[0][0], srcs[0][2]), u, (pieces[0][0], pieces[0][2]), s2d, (pieces[1][0], pieces[1][2]), cin, B, H, W)
             if s2d and info is not None:
                 info["wrote_s2d"] |= 1 << piece_dst[0][0]
-            wino_stats["launches"] += 1
+            _count_launches(1)
             return "winograd:3,%d,%d" % (cin // 8, 6 if s2d else 5)
         if (pieces and not wide and len(pieces) <= (2 if relu_of is None else 1) and all(p_[0] % 8 == 0 and p_[2] % 2 == 0 for p_ in pieces)
                 and all(lib.ynet_conv2d_winograd_supported(B, H, W, cin, p_[1], K) for p_ in pieces)):
-            cache, what = wino
             one32 = len(pieces) == 1 and pieces[0][1] == 32
             wb_out = wbits_out if (one32 and relu and relu_of is None) else None      # the forward launch of a conv -> ReLU -> conv chain writes the mask word
             wb_in = relu_wbits if (one32 and relu_of is not None and not relu and bias is None) else None      # ... and the chain's data gradient applies it
@@ -794,16 +780,12 @@ def _conv2d_raw_py(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=None, p
             tag = ("winograd:" + "+".join("%d,%d,%d" % (p_[1] // 16, cin // 8, 4 if f_ else em) for p_, f_ in zip(pieces, s2ds))
                    + ("|wbits" if wb_out is not None else ""))
             for (ptr, n, bs, col0), (di, whole), s2d in zip(pieces, piece_dst, s2ds):
-                key = "wino_%s_%d_%d" % (what, col0, n)
-                ent = cache.get(key)
-                if ent is None or ent[0] is not wp:
-                    ent = cache[key] = _wino_made((wp, winograd_filter(wp, cin, n, col0, ctot)))
-                _wino_ready(ent)
-                conv2d_winograd_raw((srcs[0][0], srcs[0][2]), ent[1], None if bias is None else bias[col0:col0 + n], (ptr, bs), cin, n, B, H, W, relu,
+                u = _wino_filter(wino, "wino", wp, 0, (cin,), n, col0, ctot).u
+                conv2d_winograd_raw((srcs[0][0], srcs[0][2]), u, None if bias is None else bias[col0:col0 + n], (ptr, bs), cin, n, B, H, W, relu,
                                     relu_of=None if wb_in is not None else relu_of, wbits_out=wb_out, relu_wbits=wb_in, **({"s2d": True} if s2d else {}))
                 if s2d and info is not None:
                     info["wrote_s2d"] |= 1 << di
-                wino_stats["launches"] += 1
+                _count_launches(1)
             return tag
         # the slice form for what the kernels above do not serve: 64 input channels, destinations of 64 channels (one launch per
         # destination over its slice of the filter; a destination nobody wants is not computed)
@@ -818,17 +800,12 @@ def _conv2d_raw_py(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=None, p
             return "winograd16:" + "+".join("%d" % (1 if relu_of is not None else 0) for _ in wanted)
         if (pieces and wide and len(pieces) <= (2 if relu_of is None else 1) and all(p_[0] % 8 == 0 and p_[2] % 2 == 0 for p_ in pieces)
                 and all(lib.ynet_conv2d_winograd_supported(B, H, W, cin, p_[1], K) for p_ in pieces)):      # (YNET_WINOGRAD16=0)
-            cache, what = wino
             tag = "winograd:" + "+".join("%d,%d,%d" % (p_[1] // 16, cin // 8, 1 if relu_of is not None else 0) for p_ in pieces)
             for ptr, n, bs, col0 in pieces:
-                key = "wino_%s_%d_%d" % (what, col0, n)
-                ent = cache.get(key)
-                if ent is None or ent[0] is not wp:
-                    ent = cache[key] = _wino_made((wp, winograd_filter(wp, cin, n, col0, ctot)))
-                _wino_ready(ent)
-                conv2d_winograd_raw((srcs[0][0], srcs[0][2]), ent[1], None if bias is None else bias[col0:col0 + n], (ptr, bs), cin, n, B, H, W, relu,
+                u = _wino_filter(wino, "wino", wp, 0, (cin,), n, col0, ctot).u
+                conv2d_winograd_raw((srcs[0][0], srcs[0][2]), u, None if bias is None else bias[col0:col0 + n], (ptr, bs), cin, n, B, H, W, relu,
                                     relu_of=relu_of)
-                wino_stats["launches"] += 1
+                _count_launches(1)
             return tag
     if (wino is not None and _wino_allowed and K == 3 and mask is None and relu_of is None and all(len(s_) == 3 for s_ in srcs)
             and (len(srcs) > 1 or srcs[0][1] not in (16, 32)) and all(s_[0] % 16 == 0 and s_[2] % 4 == 0 for s_ in srcs)):
@@ -844,36 +821,20 @@ def _conv2d_raw_py(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=None, p
                     and lib.ynet_conv2d_winograd_cat_supported(B, H, W, (ctypes.c_int * len(rest_c))(*rest_c), len(rest_c), 32, K)):
                 # 57 .. 88 input channels (the 64 / 65 -> 32 layers at 128^2): two launches -- the first 32 channels into the destination,
                 # then the rest with the destination as the additive term in front of bias and ReLU (read and written by the same lane)
-                cache, what = wino
-                key = "wino_split_" + what
-                ent = cache.get(key)
-                rc = (ctypes.c_int * len(rest_c))(*rest_c)
-                if ent is None or ent[0] is not wp or ent[3] != tuple(rest_c):
-                    cols_pad = -(-32 // 64) * 64
-                    u0 = winograd_filter(wp, 32, 32, 0, 32)
-                    u1 = torch.empty(lib.ynet_winograd_filter_cat_floats(rc, len(rest_c), 32), device=wp.device, dtype=torch.float32)
-                    L.check(lib.ynet_winograd_filter_cat(wp.data_ptr() + 4 * 32 * 9 * cols_pad, u1.data_ptr(), rc, len(rest_c), 32, 0, 32, _stream()), lib)
-                    ent = cache[key] = _wino_made((wp, u0, u1, tuple(rest_c)))
-                _wino_ready(ent)
+                u0 = _wino_filter(wino, "wino", wp, 0, (32,), 32, 0, 32).u
+                u1 = _wino_filter(wino, "cat", wp, 32, rest_c, 32, 0, 32).u
                 HW = H * W
-                conv2d_winograd_raw((first[0], first[2]), ent[1], None, (want[0][0], want[0][2]), 32, 32, B, H, W, False)
+                conv2d_winograd_raw((first[0], first[2]), u0, None, (want[0][0], want[0][2]), 32, 32, B, H, W, False)
                 rsrcs = ([(first[0] + 4 * 32 * HW, first[1] - 32, first[2])] if first[1] > 32 else []) + list(srcs[1:])
                 wb_out = wbits_out if relu else None
-                conv2d_winograd_cat_raw(rsrcs, ent[2], bias, (want[0][0], want[0][2]), B, H, W, relu, addend=(want[0][0], want[0][2], 0), wbits_out=wb_out)
-                wino_stats["launches"] += 2
+                conv2d_winograd_cat_raw(rsrcs, u1, bias, (want[0][0], want[0][2]), B, H, W, relu, addend=(want[0][0], want[0][2], 0), wbits_out=wb_out)
+                _count_launches(2)
                 return "winograd_cat:2,5|wbits" if wb_out is not None else "winograd_cat:2,2"
             if lib.ynet_conv2d_winograd_cat_supported(B, H, W, cs, len(srcs), 32, K):
-                cache, what = wino
-                key = "wino_cat_" + what
-                ent = cache.get(key)
-                if ent is None or ent[0] is not wp or ent[2] != tuple(cs):
-                    u = torch.empty(lib.ynet_winograd_filter_cat_floats(cs, len(srcs), 32), device=wp.device, dtype=torch.float32)
-                    L.check(lib.ynet_winograd_filter_cat(wp.data_ptr(), u.data_ptr(), cs, len(srcs), 32, 0, 32, _stream()), lib)
-                    ent = cache[key] = _wino_made((wp, u, tuple(cs)))
-                _wino_ready(ent)
+                u = _wino_filter(wino, "cat", wp, 0, cs, 32, 0, 32).u
                 wb_out = wbits_out if relu else None
-                conv2d_winograd_cat_raw(srcs, ent[1], bias, (want[0][0], want[0][2]), B, H, W, relu, wbits_out=wb_out)
-                wino_stats["launches"] += 1
+                conv2d_winograd_cat_raw(srcs, u, bias, (want[0][0], want[0][2]), B, H, W, relu, wbits_out=wb_out)
+                _count_launches(1)
                 return "winograd_cat:2,4|wbits" if wb_out is not None else "winograd_cat:2,0"
         if len(want) == 1 and len(dsts) == 1 and want[0][0] % 8 == 0 and want[0][2] % 2 == 0:
             # the slice form: 64 output channels (the decoders' first convolutions at 64^2: cat(up-sampled 32, skip 64[, way-point map]) -> 64)
@@ -926,7 +887,7 @@ def conv2d_shared_term(x, x_times: int, rest, weight, bias, relu: bool, cache: d
         _need_gpu(t, "conv2d_shared_term")
     cout, cin, k, _ = weight.shape
     B, _, H, W = parts[0].shape
-    rest_filter(weight, c0, c1, cache)
+    wp = rest_filter(weight, c0, c1, cache)
     descs = []
     for p_ in parts:
         t, c, bs = _plane_desc(p_.detach(), "conv2d_shared_term input")
@@ -936,25 +897,22 @@ def conv2d_shared_term(x, x_times: int, rest, weight, bias, relu: bool, cache: d
     y = torch.empty((B, cout, H, W), device=weight.device, dtype=torch.float32)
     lib = _lib()
     sp, sc, sb = _arrays(descs)
-    ent = cache.get("wino_rest")
-    if (ent is not None and ent[0] is cache["rest_wp"] and ent[2] == tuple(d[1] for d in descs) and _wino_allowed and _wino_eval and k == 3
-            and _wino_cat_eval and H * W >= _wino_eval_min_hw and all(d[0] % 16 == 0 and d[2] % 4 == 0 for d in descs) and term.data_ptr() % 8 == 0
-            and lib.ynet_conv2d_winograd_cat_supported(B, H, W, (ctypes.c_int * len(descs))(*ent[2]), len(descs), cout, k)):
-        # the Winograd form of the same launch (its filter was transformed by rest_filter_winograd, before the sweep's streams fork)
-        conv2d_winograd_cat_raw(descs, ent[1], bias.detach() if bias is not None else None, (y.data_ptr(), cout * H * W), B, H, W, relu,
-                                addend=(term.data_ptr(), cout * H * W, term.shape[0]))
-        wino_stats["launches"] += 1
-        return y
-    ent16 = cache.get("wino16_rest")
-    if (ent16 is not None and ent16[0] is cache["rest_wp"] and ent16[2] == tuple(d[1] for d in descs) and _wino_eval and k == 3
-            and _wino_cat_eval and H * W >= _wino_eval_min_hw and all(d[0] % 16 == 0 and d[2] % 4 == 0 for d in descs) and term.data_ptr() % 8 == 0
-            and _wino16_supported([d[1] for d in descs], cout, B, H, W, k)):
-        conv2d_winograd16_raw(descs, ent16[1], bias.detach() if bias is not None else None, (y.data_ptr(), cout * H * W), cout, B, H, W, relu,
-                              addend=(term.data_ptr(), cout * H * W, term.shape[0]))
-        wino_stats["launches"] += 1
-        wino_stats["launches16"] = wino_stats.get("launches16", 0) + 1
-        return y
-    L.check(lib.ynet_conv2d_add(sp, sc, sb, None, len(descs), cache["rest_wp"].data_ptr(),
+    cs = [d[1] for d in descs]
+    if (_wino_eval and k == 3 and _wino_cat_eval and H * W >= _wino_eval_min_hw and all(d[0] % 16 == 0 and d[2] % 4 == 0 for d in descs)
+            and term.data_ptr() % 8 == 0):
+        # the Winograd forms of the same launch, where rest_filter_winograd transformed their filter (before the sweep's streams fork)
+        b, dst, addend = bias.detach() if bias is not None else None, (y.data_ptr(), cout * H * W), (term.data_ptr(), cout * H * W, term.shape[0])
+        ent = _wino_filter((cache, "rest"), "cat", wp, 0, cs, cout, 0, cout, make=False)
+        if ent is not None and _wino_allowed and lib.ynet_conv2d_winograd_cat_supported(B, H, W, sc, len(descs), cout, k):
+            conv2d_winograd_cat_raw(descs, ent.u, b, dst, B, H, W, relu, addend=addend)
+            _count_launches(1)
+            return y
+        ent = _wino_filter((cache, "rest"), "wino16", wp, 0, cs, cout, 0, cout, make=False)
+        if ent is not None and _wino16_supported(cs, cout, B, H, W, k):
+            conv2d_winograd16_raw(descs, ent.u, b, dst, cout, B, H, W, relu, addend=addend)
+            _count_launches(1, slice_form=True)
+            return y
+    L.check(lib.ynet_conv2d_add(sp, sc, sb, None, len(descs), wp.data_ptr(),
                                 bias.detach().data_ptr() if bias is not None else None, y.data_ptr(), cout, cout * H * W,
                                 B, H, W, k, 1 if relu else 0, term.data_ptr(), cout * H * W, term.shape[0], _stream()), lib)
     return y
@@ -973,34 +931,21 @@ def rest_filter(weight, c0: int, c1: int, cache: dict) -> torch.Tensor:
 
 
 def rest_filter_winograd(weight, c0: int, c1: int, cache: dict, src_c, B: int, H: int, W: int):
-    """The Winograd-domain form of rest_filter(...) for sources of src_c channels each (conv2d_shared_term's launches), where
-    ynet_conv2d_winograd_cat serves them; like rest_filter it is made on the caller's stream before the sweep's streams fork."""
+    """The Winograd-domain form of rest_filter(...) for sources of src_c channels each (conv2d_shared_term's launches), where ynet_conv2d_winograd_cat or
+    the slice form serves them at this batch size; like rest_filter it is made on the caller's stream before the sweep's streams fork.  The two forms are
+    two entries of the layer's cache: another batch size adds the other one, and a captured sweep keeps reading its own."""
     wp = rest_filter(weight, c0, c1, cache)
     cout, k = weight.shape[0], weight.shape[2]
-    src_c = tuple(int(c) for c in src_c if c > 0)
-    lib = _lib()
-    cs = (ctypes.c_int * len(src_c))(*src_c)
-    if not (_wino_allowed and _wino_eval and k == 3 and src_c and lib.ynet_conv2d_winograd_cat_supported(B, H, W, cs, len(src_c), cout, k)):
-        cache.pop("wino_rest", None)
-        # the slice form (64 output channels: the 64^2 / 32^2 levels of evaluate()'s folded batches)
-        if _wino_eval and src_c and _wino16_supported(list(src_c), cout, B, H, W, k):
-            ent = cache.get("wino16_rest")
-            if ent is None or ent[0] is not wp or ent[2] != src_c:
-                with torch.no_grad():
-                    u = torch.empty(lib.ynet_winograd16_filter_floats(cs, len(src_c), cout), device=wp.device, dtype=torch.float32)
-                    L.check(lib.ynet_winograd16_filter(wp.data_ptr(), u.data_ptr(), cs, len(src_c), cout, 0, cout, _stream()), lib)
-                ent = cache["wino16_rest"] = (wp, u, src_c)
-            return ent[1]
-        cache.pop("wino16_rest", None)
+    src_c = [int(c) for c in src_c if c > 0]
+    if not (_wino_eval and k == 3 and src_c):
         return None
-    cache.pop("wino16_rest", None)
-    ent = cache.get("wino_rest")
-    if ent is None or ent[0] is not wp or ent[2] != src_c:
-        with torch.no_grad():
-            u = torch.empty(lib.ynet_winograd_filter_cat_floats(cs, len(src_c), cout), device=wp.device, dtype=torch.float32)
-            L.check(lib.ynet_winograd_filter_cat(wp.data_ptr(), u.data_ptr(), cs, len(src_c), cout, 0, cout, _stream()), lib)
-        ent = cache["wino_rest"] = (wp, u, src_c)
-    return ent[1]
+    if _wino_allowed and _lib().ynet_conv2d_winograd_cat_supported(B, H, W, (ctypes.c_int * len(src_c))(*src_c), len(src_c), cout, k):
+        kind = "cat"
+    elif _wino16_supported(src_c, cout, B, H, W, k):      # the slice form (64 output channels: the 64^2 / 32^2 levels of evaluate()'s folded batches)
+        kind = "wino16"
+    else:
+        return None
+    return _wino_filter((cache, "rest"), kind, wp, 0, src_c, cout, 0, cout).u
 
 
 def shared_conv_term(x: torch.Tensor, weight, c0: int, c1: int, cache: dict) -> torch.Tensor:
@@ -1018,6 +963,48 @@ def _weight_key(weight, lora_a, lora_b):
     if lora_a is not None:
         key += (lora_a.data_ptr(), lora_a._version, lora_b.data_ptr(), lora_b._version)
     return key
+
+
+class _Filter:
+    """One transformed filter of a layer's cache: the tensor `u`, the filter `wp` it was made from (kept alive), and the stream and event of the launch
+    that made it."""
+    __slots__ = ("wp", "u", "stream", "event")
+
+    def __init__(self, wp, u):
+        self.wp, self.u, self.stream, self.event = wp, u, None, None
+
+    def made(self):
+        """The transform was just enqueued on the current stream: remember that stream and an event behind the launch (not inside a capture)."""
+        self.stream = self.event = None
+        if torch.cuda.is_available() and not torch.cuda.is_current_stream_capturing():
+            self.stream, self.event = torch.cuda.current_stream().cuda_stream, torch.cuda.Event()
+            self.event.record()
+
+    def ready(self):
+        """Filters are transformed lazily at a layer's first Winograd launch -- possibly on one of evaluate()'s two sweep streams, with the other stream's
+        cache hit a few microseconds behind and no dependency on the transform: a hit from another stream waits for the maker's event until that has
+        completed (the first call of a process only; never inside a capture, which follows an eager pass)."""
+        if self.event is not None and not torch.cuda.is_current_stream_capturing():
+            cur = torch.cuda.current_stream()
+            if cur.cuda_stream != self.stream and not self.event.query():
+                cur.wait_event(self.event)
+
+
+def _filter(cache: dict, key: tuple, wp, make):
+    """Find or make the transformed filter cache[key] of a layer's cache (the dict _cached clears when the layer's weights change): make() -> tensor enqueues
+    the transform of `wp` on the current stream; make None: None on a miss.  THE RULE: `key` names everything the layout depends on, so an entry is never
+    overwritten by another layout, resized or popped -- a captured graph reads it at its address for as long as the weights stand.  An entry is stale only
+    when it was made from another filter than `wp`, and is then made again under the same key: a caller that went around _cached, or the "rest" entries, whose
+    packed filter rest_filter re-packs (without clearing the dict) when the weight's version changes."""
+    ent = cache.get(key)
+    if ent is not None and ent.wp is wp:
+        ent.ready()
+        return ent
+    if make is None:
+        return None
+    ent = cache[key] = _Filter(wp, make())
+    ent.made()
+    return ent
 
 
 def _cached(cache: dict, weight, lora_a, lora_b, scale, what: str):
@@ -1949,15 +1936,11 @@ class _UpConvFn(torch.autograd.Function):
         wp = _cached(cache, weight, None, None, 1.0, "fwd")
         if _lib().ynet_upsample2x_conv2d_winograd_supported(B, H, W, cin, cout, 3) == 2:      # the slice form: its own filter layout
             ent = _wino16_filter((cache, "fwd"), wp, 0, (cin,), cout, 0, cout)
-        else:
-            key = "wino_fwd_0_%d" % cout      # (the entry ops.conv2d_raw keeps for the unfused launch of the same layer)
-            ent = cache.get(key)
-            if ent is None or ent[0] is not wp:
-                ent = cache[key] = _wino_made((wp, winograd_filter(wp, cin, cout, 0, cout)))
-            _wino_ready(ent)
+        else:      # (the entry _conv2d_raw_py keeps for the unfused launch of the same layer)
+            ent = _wino_filter((cache, "fwd"), "wino", wp, 0, (cin,), cout, 0, cout)
         y = torch.empty((B, cout, H, W), device=x.device, dtype=torch.float32)
-        upsample2x_conv2d_raw((x.data_ptr(), cin * Hl * Wl), ent[1], bias.detach() if bias is not None else None, (y.data_ptr(), cout * H * W), cin, cout, B, H, W)
-        wino_stats["launches"] += 1
+        upsample2x_conv2d_raw((x.data_ptr(), cin * Hl * Wl), ent.u, bias.detach() if bias is not None else None, (y.data_ptr(), cout * H * W), cin, cout, B, H, W)
+        _count_launches(1)
         upconv_stats["fused"] += 1
         ctx.cache, ctx.shape, ctx.cout = cache, (B, cin, Hl, Wl), cout
         ctx.w_key = _weight_key(weight, None, None)
@@ -2209,14 +2192,10 @@ class _PredBCEFn(torch.autograd.Function):
                 expected_grad = float(expected_grad)
                 if not (expected_grad != 0.0 and abs(expected_grad) < float("inf")):
                     expected_grad = 1.0
-                ccache = dfr["cache"]
-                ent = ccache.get("wino_fwd_0_32")       # (the entry ops.conv2d_raw keeps for the unfused launch of the same layer)
-                if ent is None or ent[0] is not dfr["wp"]:
-                    ent = ccache["wino_fwd_0_32"] = _wino_made((dfr["wp"], winograd_filter(dfr["wp"], 32, 32, 0, 32)))
-                _wino_ready(ent)
+                u = _wino_filter((dfr["cache"], "fwd"), "wino", dfr["wp"], 0, (32,), 32, 0, 32).u      # (the entry _conv2d_raw_py keeps for the unfused launch of the same layer)
                 ctx.dx = torch.empty_like(x)
                 ctx.dy = None
-                conv2d_winograd_pred_bce_raw(dfr["src"], ent[1], dfr["bias"], wp, bias.detach() if bias is not None else None, cout, pos, tmpl, y, loss, ctx.dx, ws,
+                conv2d_winograd_pred_bce_raw(dfr["src"], u, dfr["bias"], wp, bias.detach() if bias is not None else None, cout, pos, tmpl, y, loss, ctx.dx, ws,
                                              B, H, W, expected_grad)
                 bce_blob_stats["launches"] += 1
                 conv_pred_bce_stats["fused"] += 1

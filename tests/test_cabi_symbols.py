@@ -82,6 +82,8 @@ def test_conv2d_auto_plans_the_benchmarked_layers_without_a_gpu():
     L = pkg("_lib")
     lib = L.load()
 
+    layouts = []
+
     def plan(B, H, W, srcs, dsts, K=3, relu=True, flags=0, **ops):
         d, tk = L.ConvAuto(), L.ConvTaken()
         d.nsrc, d.ndst = len(srcs), len(dsts)
@@ -95,7 +97,15 @@ def test_conv2d_auto_plans_the_benchmarked_layers_without_a_gpu():
         assert lib.ynet_conv2d_auto_plan(ctypes.byref(d), ctypes.byref(tk)) == 0, lib.ynet_last_error()
         need = lib.ynet_conv2d_auto_cache_floats(ctypes.byref(d))
         assert (need > 0) == (tk.family != 0)
+        floats = ctypes.c_longlong(-2)
+        layouts.append((lib.ynet_conv2d_auto_cache_layout(ctypes.byref(d), ctypes.byref(floats)), floats.value))
+        assert floats.value == need and (layouts[-1][0] != 0) == (need > 0)
+        assert lib.ynet_conv2d_auto_cache_layout(ctypes.byref(d), None) == layouts[-1][0]      # (the size is optional)
         return tk.family, tk.variant, tk.nlaunch
+
+    def layout(*a, **k):
+        plan(*a, **k)
+        return layouts[-1]
 
     B = 32
     assert plan(B, 256, 256, [6, 8], [32], pooled=256)[0] == 2                       # encoder.0 + ReLU + MaxPool (conv_wino_cat_kernel<2, 3 | 6>)
@@ -114,3 +124,22 @@ def test_conv2d_auto_plans_the_benchmarked_layers_without_a_gpu():
     assert plan(B, 256, 256, [32], [12], K=1, relu=False)[0] == 0                    # the 1x1 predictor
     assert plan(B, 256, 256, [32], [32], flags=L.AUTO_NO_WINOGRAD)[0] == 0
     assert plan(10, 128, 128, [32], [32])[0] == 1 and plan(4, 64, 64, [32], [32])[0] == 0      # batch 10 still Winograd at 128^2; too few pixels -> implicit GEMM
+    # ynet_conv2d_auto_cache_layout names the layout of the filter cache: the batch size moves [32] -> [32] at 128^2 from the slice form (B 3..7) to the plain
+    # form (B >= 8) -- the same 16384 floats, laid out differently: two caches; below that the implicit GEMM keeps no transformed filter
+    assert plan(8, 128, 128, [32], [32])[:2] == (1, 21) and plan(4, 128, 128, [32], [32])[:2] == (3, 22)
+    l8, l32, l4 = layout(8, 128, 128, [32], [32]), layout(32, 128, 128, [32], [32]), layout(4, 128, 128, [32], [32])
+    assert l8 == l32 and l8[0] != 0 and l8[1] == 16384
+    assert l4[0] != l8[0] and l4[0] != 0 and l4[1] == 16384
+    assert layout(2, 128, 128, [32], [32]) == (0, 0)
+    d = L.ConvAuto()      # an up-convolution's backward (32 -> 16 at 128^2 -> 256^2): its cache always holds the effective filter and the ring tables
+    d.nsrc = d.ndst = 1
+    d.src[0], d.src_c[0], d.src_bs[0] = 256, 64, 64 * 128 * 128
+    d.dst[0], d.dst_c[0], d.dst_bs[0] = 256, 32, 32 * 128 * 128
+    d.wp, d.B, d.H, d.W, d.K, d.flags = 256, 8, 128, 128, 3, L.AUTO_UPCONV_BWD
+    floats = ctypes.c_longlong(0)
+    up = lib.ynet_conv2d_auto_cache_layout(ctypes.byref(d), ctypes.byref(floats))
+    assert up != 0 and floats.value == lib.ynet_conv2d_auto_cache_floats(ctypes.byref(d)) > 0
+    d.flags = 0      # (the same operands as a plain data gradient: another layout)
+    assert lib.ynet_conv2d_auto_cache_layout(ctypes.byref(d), None) not in (0, up)
+    d.flags, d.K = L.AUTO_UPCONV_BWD, 5      # no such form: 0, *floats = -1 and the reason
+    assert lib.ynet_conv2d_auto_cache_layout(ctypes.byref(d), ctypes.byref(floats)) == 0 and floats.value == -1 and b"upconv_bwd" in lib.ynet_last_error()

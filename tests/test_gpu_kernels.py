@@ -872,6 +872,36 @@ def test_winograd_shared_skip_term_launch(dev):
     close(outs[0], ref, rtol=1e-4, scale_rel=2e-6, msg="vs torch")
 
 
+def test_rest_filter_forms_coexist_in_the_layer_cache(dev):
+    """The shared-term launch over (32, 1) channels -> 32 at 128^2 takes the slice form at B 4 and the concatenated-source form at B 8 (evaluate() on folds of
+    different sizes): the two transformed filters are two entries of the layer's cache.  Making the second leaves the first where it is, bit for bit (a captured
+    sweep reads it at that address), a later call finds both again, and each batch size launches its own form."""
+    ops = pkg("ops")
+    H = W = 128
+    up, wmap = torch.relu(rnd(8, 32, H, W, seed=1)).to(dev), torch.relu(rnd(8, 1, H, W, seed=2)).to(dev)
+    skip = torch.relu(rnd(8, 16, H, W, seed=3)).to(dev)
+    w, bias = rnd(32, 49, 3, 3, seed=4, scale=0.2).to(dev), rnd(32, seed=5).to(dev)
+    cache = {}
+    kinds = lambda: sorted(k[0] for k in cache if isinstance(k, tuple))      # noqa: E731
+    with torch.no_grad():
+        u4 = ops.rest_filter_winograd(w, 32, 48, cache, (32, 1), 4, H, W)
+        assert u4 is not None and kinds() == ["wino16"]
+        addr4, kept4 = u4.data_ptr(), u4.clone()
+        u8 = ops.rest_filter_winograd(w, 32, 48, cache, (32, 1), 8, H, W)
+        assert u8 is not None and kinds() == ["cat", "wino16"] and u8.data_ptr() != addr4
+        addr8, kept8 = u8.data_ptr(), u8.clone()
+        again4, again8 = ops.rest_filter_winograd(w, 32, 48, cache, (32, 1), 4, H, W), ops.rest_filter_winograd(w, 32, 48, cache, (32, 1), 8, H, W)
+        assert again4.data_ptr() == addr4 and again8.data_ptr() == addr8 and kinds() == ["cat", "wino16"]
+        for B, slice_launches in ((8, 0), (4, 1)):
+            term = ops.shared_conv_term(skip[:B], w, 32, 48, cache)
+            n0, n16 = ops.wino_stats["launches"], ops.wino_stats.get("launches16", 0)
+            y = ops.conv2d_shared_term(None, 1, [up[:B], wmap[:B]], w, bias, True, cache, term, 32, 48)
+            assert ops.wino_stats["launches"] - n0 == 1 and ops.wino_stats.get("launches16", 0) - n16 == slice_launches, B
+            ref = torch.relu(F.conv2d(torch.cat([up[:B], skip[:B], wmap[:B]], 1), w, bias, padding=1))
+            close(y, ref, rtol=1e-4, scale_rel=2e-6, msg=f"shared term at B {B} vs torch")
+    assert torch.equal(again4, kept4) and torch.equal(again8, kept8)
+
+
 def test_winograd_path_of_the_model_layer_and_its_switch(dev):
     """ops.conv2d takes the Winograd kernel for a plain 32 -> 32 layer -- forward AND data gradient -- and the implicit GEMM with
     YNET_WINOGRAD off; outputs and input gradients of the two agree within fp32 rounding.  (A layer without ReLU: behind a ReLU
@@ -962,7 +992,7 @@ def test_upsample_and_up_convolution_in_one_launch(dev, case):
     w = rnd(cout, cin, 3, 3, seed=2, scale=0.2).to(dev)
     bias = rnd(cout, seed=3).to(dev) if has_bias else None
     wp = ops.pack_weight(w, 0)
-    u = ops.winograd_filter(wp, cin, cout) if kind == 1 else ops._wino16_filter(({}, "fwd"), wp, 0, (cin,), cout, 0, cout)[1]
+    u = ops.winograd_filter(wp, cin, cout) if kind == 1 else ops._wino16_filter(({}, "fwd"), wp, 0, (cin,), cout, 0, cout).u
     got = torch.full((B, cout, H, W), float("nan"), device=dev)
     ops.upsample2x_conv2d_raw((x.data_ptr(), cin * Hl * Wl), u, bias, (got.data_ptr(), cout * H * W), cin, cout, B, H, W)
     up = ops.upsample2x(x)

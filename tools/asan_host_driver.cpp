@@ -247,6 +247,8 @@ int main() {
         d.dst[0] = fp; d.dst_c[0] = 32; d.dst_bs[0] = 32ll * 256 * 256; d.B = 8; d.H = 256; d.W = 256; d.K = 3; d.relu = 1;
         const long long need = ynet_conv2d_auto_cache_floats(&d);
         if (need != ynet_winograd_filter_floats(32, 32)) { fprintf(stderr, "conv2d_auto cache floats %lld\n", need); ++failures; }
+        long long lf = 0;
+        if (ynet_conv2d_auto_cache_layout(&d, &lf) == 0 || lf != need) { fprintf(stderr, "conv2d_auto cache layout: %lld floats\n", lf); ++failures; }
         EXPECT_REJECT(ynet_conv2d_auto(&d, nullptr, nullptr));                   // a Winograd plan without a cache
         d.flags = YNET_AUTO_NO_WINOGRAD;
         if (ynet_conv2d_auto_cache_floats(&d) != 0) { fprintf(stderr, "conv2d_auto: implicit GEMM needs no cache\n"); ++failures; }

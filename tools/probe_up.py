@@ -28,7 +28,7 @@ for (B, H, W, cin, cout) in [(32, 128, 128, 64, 32), (256, 128, 128, 64, 32), (3
     xl = torch.relu(torch.randn(B, cin, H // 2, W // 2, device=dev))
     w = torch.randn(cout, cin, 3, 3, device=dev) * 0.2
     wp = ops.pack_weight(w, 0)
-    u = ops._wino16_filter(({}, "fwd"), wp, 0, (cin,), cout, 0, cout)[1]
+    u = ops._wino16_filter(({}, "fwd"), wp, 0, (cin,), cout, 0, cout).u
     y = torch.empty(B, cout, H, W, device=dev)
     up = ops.upsample2x(xl)
     cache = {}
