@@ -513,6 +513,27 @@ int ynet_pred_softargmax(const float* x, long long x_bs, const float* w, const f
 int ynet_sigmoid_temp(const float* x, float* y, long long B, int C, long long HW, const int* sel, int nsel,
                       float temperature, void* stream);
 
+/* Likelihood scores of the goal map: the distribution that evaluate() samples its goals and way-points from is
+ * sigmoid(pred_goal_map / temperature) (utils/evaluate.py:128-131), every plane normalised by torch.multinomial inside `sampling`
+ * (utils/image_utils.py:110-135).  The reference keeps the draws and drops the distribution; this call scores it, with no draw.
+ * Per plane (b, c) of x [B][C][H][W] (batch stride `batch_stride` elements, so a channel slice needs no copy), with z = x / T,
+ * w = sigmoid(z), Z = sum w and g = the pixel (rint(gt_y), rint(gt_x)) (half-even; (x, y) = (column, row) as for ynet_score_rank_samples):
+ *   nll [B][C]     = log Z - log_sigmoid(z_g)                                  nats
+ *   entropy [B][C] = log Z - (sum w log_sigmoid(z)) / Z                        nats
+ *   hpd [B][C]     = (sum over {i : x_i >= x_g} of w_i) / Z                    mass of the smallest highest-density region holding g;
+ *                                                                              membership is decided on the raw fp32 logits (exact)
+ * One workgroup per plane, one pass over x, fp64 sums; planes that start on a 16-byte boundary and hold a multiple of 4 pixels are
+ * read in 16-byte vectors, any other plane element by element (decided per plane: nothing is assumed about alignment).
+ * Rules: a NaN logit makes all three results of its plane NaN; a -inf logit adds 0 to every sum (g on it: nll = +inf, hpd = 1);
+ * +inf is sigmoid = 1; sigmoids below fp32's normal range (z < -87) count as 0; Z == 0 makes all three NaN.  A ground truth that
+ * rounds outside the map (or is NaN): nll = hpd = NaN for that plane, entropy as usual, *status (device int, zero it first) becomes 1,
+ * and nothing outside the map is read.
+ * gt_xy [B][C][2] fp32 may be NULL when nll and hpd are NULL (entropy only); any of nll / entropy / hpd may be NULL, not all three.
+ * Refused (non-zero, ynet_last_error): null x, temperature <= 0 or not finite (or below 2.95e-39, where 1 / T is not), B, C, H or W < 1, H * W > 2^31 - 2048, batch_stride < C * H * W, no output,
+ * nll / hpd without gt_xy, gt_xy without status. */
+int ynet_map_likelihood(const float* x, long long batch_stride, const float* gt_xy, long long B, int C, int H, int W, float temperature,
+                        float* nll, float* entropy, float* hpd, int* status, void* stream);
+
 /* ---- heat-map construction -------------------------------------------------------------------- */
 /* get_patch + torch.stack (utils/image_utils.py:40-63; utils/train_epoch.py:63-78;
  * utils/evaluate.py:112-114,250-253): out[n] = tmpl[SH/2 - ry : +H, SW/2 - rx : +W] with

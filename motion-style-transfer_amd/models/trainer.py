@@ -281,13 +281,16 @@ class YNetTrainer:
         return self.val_ADE, self.val_FDE
 
     # ------------------------------------------------------------------------------------------
-    def test(self, df_test, image_path, return_preds=False, return_samples=False):
-        return self._test(df_test, image_path, return_preds=return_preds, return_samples=return_samples, **self.params)
+    def test(self, df_test, image_path, return_preds=False, return_samples=False, return_likelihood=False):
+        """``return_likelihood`` (not in the reference): evaluate() also scores the goal-map distribution against the ground truth
+        (df_metrics columns nll, nll_goal, entropy_goal, hpd_goal) and every round prints its mean NLL and calibration error."""
+        return self._test(df_test, image_path, return_preds=return_preds, return_samples=return_samples,
+                          return_likelihood=return_likelihood, **self.params)
 
     def _test(self, df_test, image_path, dataset_name, resize_factor, batch_size, n_round, obs_len, pred_len,
               waypoints, n_goal, n_traj, temperature, rel_threshold, use_TTST, use_CWS, CWS_params,
               use_raw_data=False, return_preds=False, return_samples=False, network=None, swap_semantic=False,
-              **kwargs):
+              return_likelihood=False, **kwargs):
         test_images, test_loader, self.homo_mat = self.prepare_data(
             df_test, image_path, dataset_name, "test", obs_len, pred_len, resize_factor, use_raw_data)
         model = self.model.to(self.device)
@@ -301,10 +304,15 @@ class YNetTrainer:
                 model, test_loader, test_images, self.device, dataset_name, self.homo_mat, input_template, waypoints,
                 "test", n_goal, n_traj, obs_len, batch_size, resize_factor, temperature, use_TTST, use_CWS,
                 rel_threshold, CWS_params, return_preds=return_preds, return_samples=return_samples,
-                network=network, swap_semantic=swap_semantic, dp=self.dp)
+                network=network, swap_semantic=swap_semantic, dp=self.dp, return_likelihood=return_likelihood)
             list_metrics.append(df_metrics)
             list_trajs.append(trajs_dict)
             print(f"Round {e}: \nTest ADE: {test_ADE} \nTest FDE: {test_FDE}")
+            if return_likelihood:
+                from ..utils.likelihood import calibration_curve
+                hpd_goal = df_metrics["hpd_goal"].to_numpy()      # (all NaN when every goal lies outside its map: nothing to calibrate)
+                ece = calibration_curve(hpd_goal)[2] if np.isfinite(hpd_goal).any() else "n/a"
+                print(f"Test NLL: {df_metrics['nll'].mean()} \nTest goal ECE: {ece}")
             self.eval_ADE.append(test_ADE)
             self.eval_FDE.append(test_FDE)
         avg_ade = sum(self.eval_ADE) / len(self.eval_ADE)

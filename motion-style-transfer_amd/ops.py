@@ -2844,6 +2844,56 @@ def check_gather_status():
             raise RuntimeError("gather_rows: an index lies outside the source")
 
 
+_likelihood_status = {}
+LIKELIHOOD_OUTPUTS = ("nll", "entropy", "hpd")
+
+
+def map_likelihood(x: torch.Tensor, gt_xy=None, temperature: float = 1.0, want: Sequence[str] = LIKELIHOOD_OUTPUTS):
+    """Likelihood scores of the distribution `sampling` draws from (ynet_map_likelihood; utils/evaluate.py:128-131,
+    utils/image_utils.py:110-135): per plane of x [B, C, H, W], p = sigmoid(x / T) normalised to sum 1, in one pass over x.
+    gt_xy [B, C, 2] (x, y) = (column, row) device coordinates, rounded half-even to a pixel g; None for the entropy alone.
+    -> dict of [B, C] device tensors, one per name in ``want``: "nll" = -log p_g (nats), "entropy" (nats), "hpd" = the mass of
+    {p >= p_g}, membership decided on the raw logits.  A channel view such as x[:, 1:3] is read in place.  Not differentiable.
+    A ground truth outside the map gives NaN nll / hpd for its plane and raises at the next check_likelihood_status()."""
+    want = tuple(want)
+    if not want or len(set(want)) != len(want) or any(w not in LIKELIHOOD_OUTPUTS for w in want):
+        raise ValueError(f"map_likelihood: want {want!r}: a non-empty selection of {LIKELIHOOD_OUTPUTS} is expected")
+    t, c, bs = _plane_desc(x.detach() if torch.is_tensor(x) else x, "map_likelihood")
+    B, _, H, W = t.shape
+    if not (float(temperature) > 0 and np.isfinite(float(temperature))):
+        raise ValueError(f"map_likelihood: temperature {temperature!r} must be positive and finite")
+    dev = t.device
+    gt = st = None
+    if gt_xy is None:
+        if "nll" in want or "hpd" in want:
+            raise ValueError("map_likelihood: nll and hpd need the ground truth; without gt_xy ask for want=('entropy',)")
+    else:
+        _need_gpu(gt_xy, "map_likelihood gt_xy", dtypes=(torch.float32, torch.float64))
+        if tuple(gt_xy.shape) != (B, c, 2):
+            raise ValueError(f"map_likelihood: gt_xy {tuple(gt_xy.shape)} does not go with the map {tuple(t.shape)} (expected {(B, c, 2)})")
+        gt = gt_xy.detach().float().contiguous()
+        st = _status_flag(_likelihood_status, dev)
+    out = {w: torch.empty((B, c), device=dev, dtype=torch.float32) for w in want}
+    ptr = {w: (out[w].data_ptr() if w in out else None) for w in LIKELIHOOD_OUTPUTS}
+    lib = _lib()
+    L.check(lib.ynet_map_likelihood(t.data_ptr(), bs, gt.data_ptr() if gt is not None else None, B, c, H, W, float(temperature),
+                                    ptr["nll"], ptr["entropy"], ptr["hpd"], st.data_ptr() if st is not None else None, _stream()), lib)
+    return out
+
+
+def check_likelihood_status(raise_error: bool = True) -> bool:
+    """Raise if a map_likelihood call met a ground truth that rounds outside its map (checked at a sync point); the flag is cleared.
+    raise_error=False: report it instead (-> True if one did) -- evaluate() keeps such a plane's NaN nll / hpd and warns."""
+    hit = False
+    for dev, st in _likelihood_status.items():
+        if int(st.item()) != 0:
+            st.zero_()
+            hit = True
+    if hit and raise_error:
+        raise RuntimeError("map_likelihood: a ground-truth position lies outside the map (its nll and hpd are NaN)")
+    return hit
+
+
 def check_patch_status():
     """Raise if a device-side coordinate ever left the template (checked at sync points)."""
     for dev, st in _patch_status.items():

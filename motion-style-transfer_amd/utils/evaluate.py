@@ -176,10 +176,16 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
              n_goal, n_traj, obs_len, batch_size, resize_factor=0.25, temperature=1, use_TTST=False, use_CWS=False,
              rel_thresh=0.002, CWS_params=None, return_preds=False, return_samples=False, network=None,
              swap_semantic=False, forced_samples=None, dp=None, max_effective_batch=256, forced_goals=None,
-             forced_ttst_samples=None):
+             forced_ttst_samples=None, return_likelihood=False):
     """utils/evaluate.py:37-315.  Extra keyword arguments (tests / data-parallel runs): ``forced_samples`` [K,B,nwp,2]
     per batch replaces every random draw, ``forced_goals`` [n_goal,B,1,2] per batch only the goal draw,
-    ``forced_ttst_samples`` [10000,B,1,2] per batch the TTST draw; ``dp`` shards each batch over ranks."""
+    ``forced_ttst_samples`` [10000,B,1,2] per batch the TTST draw; ``dp`` shards each batch over ranks.
+    ``return_likelihood`` scores the goal decoder's distribution itself -- sigmoid(pred_goal_map / T), every plane normalised, what
+    `sampling` draws from -- against the ground truth, with no draw (ops.map_likelihood): df_out gains the
+    columns ``nll`` (mean over the pred_len steps, nats), ``nll_goal``, ``entropy_goal`` and ``hpd_goal`` (last step), and with
+    ``return_preds`` trajs_dict gains ``nll_steps``, ``entropy_steps`` and ``hpd_steps`` [N, pred_len].  A step whose ground truth
+    lies outside the map has NaN nll / hpd (one warning per call).  The sweep then takes the
+    branch ``return_preds`` takes (same launches and draws otherwise; the captured sweep is neither used nor touched)."""
     model.eval()
     waypoints = list(waypoints)
     n_wp = len(waypoints)
@@ -190,6 +196,8 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
         trajs_dict = {k: [] for k in keys}
     else:
         trajs_dict = None
+    like_lists = {k: [] for k in ops.LIKELIHOOD_OUTPUTS} if return_likelihood else None
+    like_warned = False
 
     with torch.no_grad():
         # Every packed filter is (re)written HERE, on the caller's stream: the K-sample passes below run the trajectory decoder on two
@@ -197,8 +205,10 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
         # versions: in place, into the layer's persistent buffers) would be read by the other stream's cache hit with no
         # dependency on the pack kernel.  The side streams wait for this stream before their first launch.
         ops.refresh_filters(model)
+        if return_likelihood:
+            ops.check_likelihood_status()      # a report left pending by an earlier ops.map_likelihood call of the caller's is raised, not swallowed below
         plain = (forced_samples is None and forced_goals is None and not use_TTST and not use_CWS and not return_preds
-                 and not return_samples and dataset_name != "eth")
+                 and not return_samples and dataset_name != "eth" and not return_likelihood)
         sa = getattr(model, "softargmax_", None)
         hooked = sa is not None and (sa._forward_hooks or sa._forward_pre_hooks)
         graphs = None
@@ -270,6 +280,8 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                         pred_goal_map = model.pred_goal(features)
                         # sigmoid(pred_goal_map[:, waypoints] / T): channel gather + scale + sigmoid in one pass
                         wp_sigmoid = ops.sigmoid_temp(pred_goal_map, waypoints, temperature)
+                        if return_likelihood:      # every step's plane against its ground truth, in resized pixels: one launch
+                            like = ops.map_likelihood(pred_goal_map, gt_future, temperature)
 
                         if forced_samples is not None:
                             waypoint_samples = forced_samples[b][:, lo:lo + n_local].to(device)
@@ -315,11 +327,23 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                         fde = fde_batch.min(dim=0)[0][:, 0]
                     else:
                         ade = fde = torch.zeros(0, device=device)
+                        if return_likelihood:
+                            like = {k: torch.zeros((0, trajectory.shape[1] - obs_len), device=device) for k in ops.LIKELIHOOD_OUTPUTS}
                     if dp is not None:
                         sizes = dp.shard_sizes(n_global)
                         ade, fde = dp.gather_rows(ade, sizes), dp.gather_rows(fde, sizes)
+                        if return_likelihood:
+                            like = {k: dp.gather_rows(v, sizes) for k, v in like.items()}
                     ade_list.append(ade.cpu().numpy())
                     fde_list.append(fde.cpu().numpy())
+                    if return_likelihood:
+                        for k, v in like.items():
+                            like_lists[k].append(v.cpu().numpy())
+                        if ops.check_likelihood_status(raise_error=False) and not like_warned:
+                            import warnings
+                            like_warned = True
+                            warnings.warn("evaluate(return_likelihood=True): a ground-truth position lies outside the map; its nll and hpd "
+                                          "are NaN (ADE / FDE are unaffected; utils.likelihood.calibration_curve leaves NaN entries out)")
                     ops.check_patch_status()      # (the batch is synchronised by the copies above: a window that left the template raises here)
                 meta_id_list.append(meta_ids)
                 scene_id_list.append([scene_id] * n_data)
@@ -330,9 +354,18 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
     val_ade_arr, val_fde_arr = np.concatenate(ade_list), np.concatenate(fde_list)
     df_out = pd.DataFrame({"metaId": np.concatenate(meta_id_list), "sceneId": sum(scene_id_list, []),
                            "ade": val_ade_arr, "fde": val_fde_arr})
+    if return_likelihood:
+        steps = {k: np.concatenate(v, axis=0) for k, v in like_lists.items()}      # [N, pred_len] each
+        df_out["nll"] = steps["nll"].mean(axis=1)
+        df_out["nll_goal"] = steps["nll"][:, -1]
+        df_out["entropy_goal"] = steps["entropy"][:, -1]
+        df_out["hpd_goal"] = steps["hpd"][:, -1]
     if return_preds:
         for key, value in trajs_dict.items():
             trajs_dict[key] = np.concatenate(value, axis=0)
+        if return_likelihood:
+            for k, v in steps.items():
+                trajs_dict[k + "_steps"] = v
         trajs_dict["metaId"] = df_out["metaId"].to_numpy()
         trajs_dict["sceneId"] = list(df_out["sceneId"])
     return val_ade_arr.mean(), val_fde_arr.mean(), df_out, trajs_dict

@@ -13,6 +13,8 @@ that batch.  Nothing is captured into a hipGraph here; evaluate()'s captured-swe
 ``predict_styles`` is predict() for a scene whose agents wear different styles: one frozen model, the adapter sets of a
 models.style_bank.StyleBank, one call.
 """
+import inspect
+
 import numpy as np
 import torch
 
@@ -64,7 +66,25 @@ def predict(model, scene_image, observed, input_template, waypoints, n_goal, n_t
     -> dict of device tensors: ``trajectories`` [N, K, pred_len, 2] best first, in original-image pixels (the convention of
        trajs_dict["prediction"]), ``waypoints`` [N, K, n_wp, 2] (resized pixels, as sampled), ``scores`` [N, K] descending,
        ``order`` [N, K] int32 (row r is sample order[:, r] of the sweep), and with ``return_maps`` ``goal_map`` [N, pred_len, H, W]
-       and ``goal_sigmoid_map`` as evaluate(return_samples=True) stores them."""
+       and ``goal_sigmoid_map`` as evaluate(return_samples=True) stores them.
+       predict_with_entropy() is this call plus ``entropy`` [N, pred_len]: how spread out every step's goal-map distribution is."""
+    return _predict(False, **locals())
+
+
+def predict_with_entropy(*args, **kwargs):
+    """predict() with the same arguments, and one more result: ``entropy`` [N, pred_len] (device tensor), the entropy in nats of every
+    future step's goal-map distribution -- sigmoid(pred_goal_map / T) normalised per plane, what `sampling` draws from.  It needs no
+    ground truth and no draw: one ops.map_likelihood launch per chunk in its form without ground truth, the
+    values evaluate(return_likelihood=True) reports as ``entropy_steps``.  Every other result is predict()'s, bit for bit.
+    (A function of its own and not a keyword of predict(): predict()'s parameter list is pinned by tests/test_predict_host.py.)"""
+    bound = _PREDICT_SIGNATURE.bind(*args, **kwargs)
+    bound.apply_defaults()
+    return _predict(True, **bound.arguments)
+
+
+def _predict(return_entropy, model, scene_image, observed, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
+             use_TTST, use_CWS, rel_thresh, CWS_params, network, swap_semantic, batch_size, max_effective_batch, forced_samples, return_maps):
+    """The body of predict() / predict_with_entropy()"""
     waypoints = list(waypoints)
     n_wp = len(waypoints)
     n_goal, n_traj, obs_len = int(n_goal), int(n_traj), int(obs_len)
@@ -93,7 +113,8 @@ def predict(model, scene_image, observed, input_template, waypoints, n_goal, n_t
     device = next(model.parameters()).device
     was_training = model.training
     model.eval()
-    out = {k: [] for k in ["trajectories", "waypoints", "scores", "order"] + (["goal_map", "goal_sigmoid_map"] if return_maps else [])}
+    out = {k: [] for k in ["trajectories", "waypoints", "scores", "order"] + (["goal_map", "goal_sigmoid_map"] if return_maps else [])
+           + (["entropy"] if return_entropy else [])}
     try:
         with torch.no_grad():
             ops.refresh_filters(model)      # on the caller's stream, before the decoder passes fan out over two (see evaluate())
@@ -127,6 +148,8 @@ def predict(model, scene_image, observed, input_template, waypoints, n_goal, n_t
                 if return_maps:
                     out["goal_map"].append(pred_goal_map)
                     out["goal_sigmoid_map"].append(model.sigmoid(pred_goal_map / temperature))
+                if return_entropy:
+                    out["entropy"].append(ops.map_likelihood(pred_goal_map, None, temperature, want=("entropy",))["entropy"])
 
                 trajs_samples = _decoder_passes(model, features, waypoint_samples, input_template, n, n_wp, H, W, max_effective_batch, device)
                 ranked, ranked_goals, score, order = ops.score_rank_samples(wp_sigmoid, waypoint_samples, trajs_samples.contiguous(),
@@ -141,6 +164,9 @@ def predict(model, scene_image, observed, input_template, waypoints, n_goal, n_t
     return {k: (v[0] if len(v) == 1 else torch.cat(v)) for k, v in out.items()}
 
 
+_PREDICT_SIGNATURE = inspect.signature(predict)
+
+
 def predict_styles(bank, scene_image, observed, style, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
                    use_TTST=False, use_CWS=False, rel_thresh=0.002, CWS_params=None, network=None, swap_semantic=False, batch_size=None,
                    max_effective_batch=256, forced_samples=None, return_maps=False):
@@ -151,6 +177,7 @@ def predict_styles(bank, scene_image, observed, style, input_template, waypoints
     style            [N] style names or indices, one per agent (bank.names / bank.index; style_bank.BASE_STYLE = the model as loaded)
     forced_samples   as for predict(), in the CALLER's order: {first agent of a chunk: [K, n, n_wp, 2]} or one tensor [K, N, n_wp, 2]
     every other argument and every result as for predict(); the results are in the caller's order and carry ``style_index`` [N] (int64).
+    The goal-map entropy of predict_with_entropy() is out of scope here for now: there is no predict_styles form of it.
 
     Each chunk (``batch_size`` agents of the caller's order; it may hold any subset of the styles) is stable-sorted by style index on
     the host -- the labels are host data.  ynet_gather_rows builds the sorted observed coordinates and forced samples, and

@@ -209,6 +209,22 @@ int main() {
     EXPECT_REJECT(ynet_score_rank_samples(cfp, cfp, cfp, 2, 65, 1, 12, 8, 8, 4.f, fp, &status, fp, fp, &status, nullptr));      // K > 64
     EXPECT_REJECT(ynet_score_rank_samples(cfp, cfp, cfp, 2, 0, 1, 12, 8, 8, 4.f, fp, &status, fp, fp, &status, nullptr));
     EXPECT_REJECT(ynet_score_rank_samples(cfp, cfp, cfp, 2, 20, 1, 12, 8, 8, 0.f, fp, &status, fp, fp, &status, nullptr));
+    EXPECT_REJECT(ynet_map_likelihood(nullptr, 16, cfp, 1, 1, 4, 4, 1.f, fp, fp, fp, &status, nullptr));                 // no map
+    EXPECT_REJECT(ynet_map_likelihood(cfp, 16, cfp, 1, 1, 4, 4, 0.f, fp, fp, fp, &status, nullptr));                     // temperature 0
+    EXPECT_REJECT(ynet_map_likelihood(cfp, 16, cfp, 1, 1, 4, 4, -1.f, fp, fp, fp, &status, nullptr));
+    EXPECT_REJECT(ynet_map_likelihood(cfp, 16, cfp, 1, 1, 4, 4, 1.f / 0.f, fp, fp, fp, &status, nullptr));               // not finite
+    EXPECT_REJECT(ynet_map_likelihood(cfp, 16, cfp, 1, 1, 4, 4, 0.f / 0.f, fp, fp, fp, &status, nullptr));
+    EXPECT_REJECT(ynet_map_likelihood(cfp, 16, cfp, 1, 1, 4, 4, 1e-39f, fp, fp, fp, &status, nullptr));                  // a denormal: 1 / T overflows
+    EXPECT_REJECT(ynet_map_likelihood(cfp, 1ll << 31, cfp, 1, 1, 32768, 65536, 1.f, fp, fp, fp, &status, nullptr));      // 2^31 pixels per plane
+    EXPECT_REJECT(ynet_map_likelihood(cfp, 16, cfp, 0, 1, 4, 4, 1.f, fp, fp, fp, &status, nullptr));                     // B, C, H, W < 1
+    EXPECT_REJECT(ynet_map_likelihood(cfp, 16, cfp, 1, 0, 4, 4, 1.f, fp, fp, fp, &status, nullptr));
+    EXPECT_REJECT(ynet_map_likelihood(cfp, 16, cfp, 1, 1, 0, 4, 1.f, fp, fp, fp, &status, nullptr));
+    EXPECT_REJECT(ynet_map_likelihood(cfp, 16, cfp, 1, 1, 4, 0, 1.f, fp, fp, fp, &status, nullptr));
+    EXPECT_REJECT(ynet_map_likelihood(cfp, 31, cfp, 2, 2, 4, 4, 1.f, fp, fp, fp, &status, nullptr));                     // batch stride below the image
+    EXPECT_REJECT(ynet_map_likelihood(cfp, 16, cfp, 1, 1, 4, 4, 1.f, nullptr, nullptr, nullptr, &status, nullptr));      // no output
+    EXPECT_REJECT(ynet_map_likelihood(cfp, 16, nullptr, 1, 1, 4, 4, 1.f, fp, fp, nullptr, &status, nullptr));            // nll without the ground truth
+    EXPECT_REJECT(ynet_map_likelihood(cfp, 16, nullptr, 1, 1, 4, 4, 1.f, nullptr, fp, fp, &status, nullptr));            // hpd without the ground truth
+    EXPECT_REJECT(ynet_map_likelihood(cfp, 16, cfp, 1, 1, 4, 4, 1.f, fp, fp, fp, nullptr, nullptr));                     // ground truth without a status flag
     EXPECT_REJECT(ynet_resize_nearest(nullptr, (int*)dummy, 4, 4, 2, 2, 0.5, 0.5, nullptr));
     EXPECT_REJECT(ynet_resize_nearest((const int*)dummy, (int*)dummy, 4, 4, 2, 2, 0.0, 0.5, nullptr));      // factor 0
     EXPECT_REJECT(ynet_upconv_dgrad_ring(nullptr, 0, cfp, nullptr, 0, fp, 0, 1, 64, 32, 8, 8, nullptr));
