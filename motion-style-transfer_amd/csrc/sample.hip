@@ -7,7 +7,8 @@
 //   cws_prior_kernel          torch_multivariate_gaussian_heatmap x sigmoid map, normalised, and its expectation
 //                             (conditioned waypoint sampling, utils/evaluate.py:9-34, 172-224)
 //   score_rank_kernel         the K sampled futures of an agent scored against the goal map and ranked (predict())
-//   score_rank_rows_kernel    the same, every agent's results written to a row of the caller's choosing (predict_styles())
+//   score_rank_rows_kernel    the same body (score_rank_body), every agent's results written to a row of the caller's choosing
+//                             (predict_styles())
 //   gather_rows_kernel        dst[i, :] = src[idx[i], :]: a style-sorted batch built from the caller's rows (predict_styles())
 //
 // Random numbers: Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11; the constants of Random123 / cuRAND / torch's
@@ -314,6 +315,12 @@ __global__ __launch_bounds__(256) void cws_prior_kernel(const float* __restrict_
 // The ranks are counted in the wave with one broadcast per sample (no LDS storage, no atomics); ds_permute sends k to lane
 // rank_k, so lane r knows the sample that takes output row r.  Rows are copied as (x, y) pairs, lanes along the output.
 // A sample that rounds to a pixel outside the map is not read: *status becomes 1 (every lane that sees one writes the same value).
+//
+// Agent b reads its own maps and samples at b.  score_rank_kernel writes score / order / ranked / ranked_goals at row b;
+// score_rank_rows_kernel (ROWS) writes them at row out_row[b], for a batch that was reordered before the sweep (predict_styles() sorts
+// the agents by style), so the results land in the caller's order from this launch (no pass over [N, K, pred_len, 2] afterwards).
+// out_row must be a permutation of 0 .. B - 1 (two agents with one row would race); an entry outside 0 .. B - 1 is never used as an
+// address: the agent's wave writes nothing and *status becomes 2.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int score_order_key(float s) {
     // a total order on the bits (a NaN score still gets a rank of its own): larger key = better sample
@@ -321,14 +328,19 @@ __device__ __forceinline__ int score_order_key(float s) {
     return b >= 0 ? b : (b ^ 0x7fffffff);
 }
 
-__global__ __launch_bounds__(256) void score_rank_kernel(const float* __restrict__ prob, const float* __restrict__ wps,
-                                                         const float* __restrict__ trajs, int B, int K, int n_wp, int pred_len, int H,
-                                                         int W, float inv_resize, float* __restrict__ score, int* __restrict__ order,
-                                                         float* __restrict__ ranked, float* __restrict__ ranked_goals,
-                                                         int* __restrict__ status) {
+template <bool ROWS>
+__device__ __forceinline__ void score_rank_body(const float* __restrict__ prob, const float* __restrict__ wps, const float* __restrict__ trajs,
+                                                const int* __restrict__ out_row, int B, int K, int n_wp, int pred_len, int H, int W,
+                                                float inv_resize, float* __restrict__ score, int* __restrict__ order,
+                                                float* __restrict__ ranked, float* __restrict__ ranked_goals, int* __restrict__ status) {
     const int lane = threadIdx.x & 63;
     const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;      // (whole waves leave; nothing below synchronises the workgroup)
+    const long long row = ROWS ? out_row[b] : b;
+    if (ROWS && (row < 0 || row >= B)) {      // (the same for all 64 lanes: the wave leaves as one)
+        *status = 2;
+        return;
+    }
     const long long plane = (long long)H * W;
     float s = 0.f;
     if (lane < K) {
@@ -354,83 +366,6 @@ __global__ __launch_bounds__(256) void score_rank_kernel(const float* __restrict
         rank += (kj > key || (kj == key && j < lane)) ? 1 : 0;
     }
     if (lane >= K) rank = lane;      // lanes past K keep their own number: the permutation stays one-to-one
-    const int src = __builtin_amdgcn_ds_permute(rank << 2, lane);      // lane r <- the sample whose rank is r
-    const float s_src = __shfl(s, src, 64);
-    if (lane < K) {
-        order[b * K + lane] = src;
-        score[b * K + lane] = s_src;
-    }
-    {
-        const float2* in = reinterpret_cast<const float2*>(trajs);
-        float2* out = reinterpret_cast<float2*>(ranked) + b * K * pred_len;
-        const int total = K * pred_len;
-        for (int i0 = 0; i0 < total; i0 += 64) {
-            const int i = i0 + lane, r = min(i, total - 1) / pred_len, t = i - r * pred_len;
-            const int k = __shfl(src, r, 64);
-            if (i < total) {
-                float2 v = in[((long long)k * B + b) * pred_len + t];
-                v.x *= inv_resize;
-                v.y *= inv_resize;
-                out[i] = v;
-            }
-        }
-    }
-    {
-        const float2* in = reinterpret_cast<const float2*>(wps);
-        float2* out = reinterpret_cast<float2*>(ranked_goals) + b * K * n_wp;
-        const int total = K * n_wp;
-        for (int i0 = 0; i0 < total; i0 += 64) {
-            const int i = i0 + lane, r = min(i, total - 1) / n_wp, w = i - r * n_wp;
-            const int k = __shfl(src, r, 64);
-            if (i < total) out[i] = in[((long long)k * B + b) * n_wp + w];
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// score_rank_kernel for a batch that was reordered before the sweep (predict_styles() sorts the agents by style): agent b of the
-// batch reads its own maps and samples at b and writes score / order / ranked / ranked_goals at row out_row[b], so the results land
-// in the caller's order from this launch (no pass over [N, K, pred_len, 2] afterwards).  Scoring rule, tie rule, NaN rule and the
-// lane layout are score_rank_kernel's.  out_row must be a permutation of 0 .. B - 1 (two agents with one row would race); an entry
-// outside 0 .. B - 1 is never used as an address: the agent's wave writes nothing and *status becomes 2.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void score_rank_rows_kernel(const float* __restrict__ prob, const float* __restrict__ wps,
-                                                              const float* __restrict__ trajs, const int* __restrict__ out_row, int B, int K,
-                                                              int n_wp, int pred_len, int H, int W, float inv_resize,
-                                                              float* __restrict__ score, int* __restrict__ order, float* __restrict__ ranked,
-                                                              float* __restrict__ ranked_goals, int* __restrict__ status) {
-    const int lane = threadIdx.x & 63;
-    const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (b >= B) return;      // (whole waves leave; nothing below synchronises the workgroup)
-    const long long row = out_row[b];
-    if (row < 0 || row >= B) {      // (the same for all 64 lanes: the wave leaves as one)
-        *status = 2;
-        return;
-    }
-    const long long plane = (long long)H * W;
-    float s = 0.f;
-    if (lane < K) {
-        const float2* wp = reinterpret_cast<const float2*>(wps) + ((long long)lane * B + b) * n_wp;
-        const float* pb = prob + b * n_wp * plane;
-        bool bad = false;
-        for (int w = 0; w < n_wp; ++w) {
-            const float2 c = wp[w];
-            const float fx = rintf(c.x), fy = rintf(c.y);
-            if (fx >= 0.f && fx < (float)W && fy >= 0.f && fy < (float)H) {
-                s += logf(pb[w * plane + (long long)fy * W + (long long)fx] + 1e-12f);
-            } else {
-                bad = true;
-            }
-        }
-        if (bad) *status = 1;
-    }
-    const int key = score_order_key(s);
-    int rank = 0;
-    for (int j = 0; j < K; ++j) {
-        const int kj = __shfl(key, j, 64);
-        rank += (kj > key || (kj == key && j < lane)) ? 1 : 0;
-    }
-    if (lane >= K) rank = lane;
     const int src = __builtin_amdgcn_ds_permute(rank << 2, lane);      // lane r <- the sample whose rank is r
     const float s_src = __shfl(s, src, 64);
     if (lane < K) {
@@ -462,6 +397,23 @@ __global__ __launch_bounds__(256) void score_rank_rows_kernel(const float* __res
             if (i < total) out[i] = in[((long long)k * B + b) * n_wp + w];
         }
     }
+}
+
+// (two __global__ functions under plain names and not one templated kernel: profiles/ and DESIGN.md name them as a profiler prints them)
+__global__ __launch_bounds__(256) void score_rank_kernel(const float* __restrict__ prob, const float* __restrict__ wps,
+                                                         const float* __restrict__ trajs, int B, int K, int n_wp, int pred_len, int H,
+                                                         int W, float inv_resize, float* __restrict__ score, int* __restrict__ order,
+                                                         float* __restrict__ ranked, float* __restrict__ ranked_goals,
+                                                         int* __restrict__ status) {
+    score_rank_body<false>(prob, wps, trajs, nullptr, B, K, n_wp, pred_len, H, W, inv_resize, score, order, ranked, ranked_goals, status);
+}
+
+__global__ __launch_bounds__(256) void score_rank_rows_kernel(const float* __restrict__ prob, const float* __restrict__ wps,
+                                                              const float* __restrict__ trajs, const int* __restrict__ out_row, int B, int K,
+                                                              int n_wp, int pred_len, int H, int W, float inv_resize,
+                                                              float* __restrict__ score, int* __restrict__ order, float* __restrict__ ranked,
+                                                              float* __restrict__ ranked_goals, int* __restrict__ status) {
+    score_rank_body<true>(prob, wps, trajs, out_row, B, K, n_wp, pred_len, H, W, inv_resize, score, order, ranked, ranked_goals, status);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -538,42 +490,44 @@ int ynet_cws_prior(const float* sig, long long sig_batch_stride, int n_persons, 
 
 // The K sampled futures of each agent, scored against the goal map and handed back best first (utils/evaluate.py:229-266 draws
 // and decodes them; utils/image_utils.py:110-135: a sample is (x, y) = (column, row) of the map).  Contiguous arrays; see the header.
+// ynet_score_rank_samples_rows is the same call for a batch the caller reordered before the sweep: agent b writes its results at row
+// out_row[b] (B device ints, a permutation of 0 .. B - 1).  `what` is the entry's name in the messages, `rows` whether it takes out_row.
+static int score_rank_launch(const char* what, bool rows, const float* prob, const float* waypoint_samples, const float* trajs,
+                             const int* out_row, int B, int K, int n_wp, int pred_len, int H, int W, float inv_resize_factor, float* score,
+                             int* order, float* ranked, float* ranked_goals, int* status, void* stream) {
+    YNET_REQUIRE(K >= 1 && K <= 64, "%s: K = %d samples per agent; one wavefront ranks 1 .. 64", what, K);
+    YNET_REQUIRE(prob && waypoint_samples && trajs && (out_row || !rows) && score && order && ranked && ranked_goals && status,
+                 "%s: null pointer", what);
+    YNET_REQUIRE(B > 0 && n_wp > 0 && pred_len > 0 && H > 0 && W > 0 && n_wp <= (1 << 16) && pred_len <= (1 << 16),
+                 "%s: bad shape B=%d n_wp=%d pred_len=%d map %dx%d", what, B, n_wp, pred_len, H, W);
+    YNET_REQUIRE(inv_resize_factor > 0.f && inv_resize_factor < INFINITY, "%s: 1 / resize_factor must be positive and finite", what);
+    YNET_REQUIRE(((reinterpret_cast<uintptr_t>(waypoint_samples) | reinterpret_cast<uintptr_t>(trajs) | reinterpret_cast<uintptr_t>(ranked) |
+                   reinterpret_cast<uintptr_t>(ranked_goals)) & 7) == 0,
+                 "%s: the (x, y) arrays must be 8-byte aligned", what);
+    YNET_REQUIRE((reinterpret_cast<uintptr_t>(out_row) & 3) == 0, "%s: out_row must be 4-byte aligned", what);
+    const dim3 grid((unsigned)ceil_div(B, 4));
+    if (rows) {
+        hipLaunchKernelGGL(score_rank_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, prob, waypoint_samples, trajs, out_row, B, K, n_wp,
+                           pred_len, H, W, inv_resize_factor, score, order, ranked, ranked_goals, status);
+    } else {
+        hipLaunchKernelGGL(score_rank_kernel, grid, dim3(256), 0, (hipStream_t)stream, prob, waypoint_samples, trajs, B, K, n_wp, pred_len, H,
+                           W, inv_resize_factor, score, order, ranked, ranked_goals, status);
+    }
+    return ynet_check_launch(what);
+}
+
 int ynet_score_rank_samples(const float* prob, const float* waypoint_samples, const float* trajs, int B, int K, int n_wp, int pred_len,
                             int H, int W, float inv_resize_factor, float* score, int* order, float* ranked, float* ranked_goals,
                             int* status, void* stream) {
-    YNET_REQUIRE(K >= 1 && K <= 64, "score_rank_samples: K = %d samples per agent; one wavefront ranks 1 .. 64", K);
-    YNET_REQUIRE(prob && waypoint_samples && trajs && score && order && ranked && ranked_goals && status,
-                 "score_rank_samples: null pointer");
-    YNET_REQUIRE(B > 0 && n_wp > 0 && pred_len > 0 && H > 0 && W > 0 && n_wp <= (1 << 16) && pred_len <= (1 << 16),
-                 "score_rank_samples: bad shape B=%d n_wp=%d pred_len=%d map %dx%d", B, n_wp, pred_len, H, W);
-    YNET_REQUIRE(inv_resize_factor > 0.f && inv_resize_factor < INFINITY, "score_rank_samples: 1 / resize_factor must be positive and finite");
-    YNET_REQUIRE(((reinterpret_cast<uintptr_t>(waypoint_samples) | reinterpret_cast<uintptr_t>(trajs) | reinterpret_cast<uintptr_t>(ranked) |
-                   reinterpret_cast<uintptr_t>(ranked_goals)) & 7) == 0,
-                 "score_rank_samples: the (x, y) arrays must be 8-byte aligned");
-    hipLaunchKernelGGL(score_rank_kernel, dim3((unsigned)ceil_div(B, 4)), dim3(256), 0, (hipStream_t)stream, prob, waypoint_samples, trajs,
-                       B, K, n_wp, pred_len, H, W, inv_resize_factor, score, order, ranked, ranked_goals, status);
-    return ynet_check_launch("score_rank_samples");
+    return score_rank_launch("score_rank_samples", false, prob, waypoint_samples, trajs, nullptr, B, K, n_wp, pred_len, H, W,
+                             inv_resize_factor, score, order, ranked, ranked_goals, status, stream);
 }
 
-// ynet_score_rank_samples for a batch the caller reordered before the sweep: agent b writes its results at row out_row[b] (see
-// score_rank_rows_kernel and the header).  out_row: B device ints, a permutation of 0 .. B - 1.
 int ynet_score_rank_samples_rows(const float* prob, const float* waypoint_samples, const float* trajs, const int* out_row, int B, int K,
                                  int n_wp, int pred_len, int H, int W, float inv_resize_factor, float* score, int* order, float* ranked,
                                  float* ranked_goals, int* status, void* stream) {
-    YNET_REQUIRE(K >= 1 && K <= 64, "score_rank_samples_rows: K = %d samples per agent; one wavefront ranks 1 .. 64", K);
-    YNET_REQUIRE(prob && waypoint_samples && trajs && out_row && score && order && ranked && ranked_goals && status,
-                 "score_rank_samples_rows: null pointer");
-    YNET_REQUIRE(B > 0 && n_wp > 0 && pred_len > 0 && H > 0 && W > 0 && n_wp <= (1 << 16) && pred_len <= (1 << 16),
-                 "score_rank_samples_rows: bad shape B=%d n_wp=%d pred_len=%d map %dx%d", B, n_wp, pred_len, H, W);
-    YNET_REQUIRE(inv_resize_factor > 0.f && inv_resize_factor < INFINITY,
-                 "score_rank_samples_rows: 1 / resize_factor must be positive and finite");
-    YNET_REQUIRE(((reinterpret_cast<uintptr_t>(waypoint_samples) | reinterpret_cast<uintptr_t>(trajs) | reinterpret_cast<uintptr_t>(ranked) |
-                   reinterpret_cast<uintptr_t>(ranked_goals)) & 7) == 0,
-                 "score_rank_samples_rows: the (x, y) arrays must be 8-byte aligned");
-    YNET_REQUIRE((reinterpret_cast<uintptr_t>(out_row) & 3) == 0, "score_rank_samples_rows: out_row must be 4-byte aligned");
-    hipLaunchKernelGGL(score_rank_rows_kernel, dim3((unsigned)ceil_div(B, 4)), dim3(256), 0, (hipStream_t)stream, prob, waypoint_samples,
-                       trajs, out_row, B, K, n_wp, pred_len, H, W, inv_resize_factor, score, order, ranked, ranked_goals, status);
-    return ynet_check_launch("score_rank_samples_rows");
+    return score_rank_launch("score_rank_samples_rows", true, prob, waypoint_samples, trajs, out_row, B, K, n_wp, pred_len, H, W,
+                             inv_resize_factor, score, order, ranked, ranked_goals, status, stream);
 }
 
 // dst[i][0 .. L) = src[idx[i]][0 .. L): the row gather predict_styles() builds its style-sorted batch with (see the header).

@@ -2480,9 +2480,7 @@ def gather_patches(template, xy, H: int, W: int) -> torch.Tensor:
         coords = torch.from_numpy(host).to(dev, non_blocking=True)
     n = coords.shape[0]
     out = torch.empty((n, H, W), device=dev, dtype=torch.float32)
-    st = _patch_status.get(dev)
-    if st is None:
-        st = _patch_status[dev] = torch.zeros(1, device=dev, dtype=torch.int32)
+    st = _status_flag(_patch_status, dev)
     lib = _lib()
     L.check(lib.ynet_gather_patch(template.data_ptr(), SH, SW, coords.data_ptr(), out.data_ptr(), n, H, W,
                                   st.data_ptr(), _stream()), lib)
@@ -2699,29 +2697,30 @@ def cws_prior(sig: torch.Tensor, mean_xy: torch.Tensor, dist_xy: torch.Tensor, s
 _score_status = {}
 
 
-def score_rank_samples(prob: torch.Tensor, waypoint_samples: torch.Tensor, trajs: torch.Tensor, resize_factor: float):
-    """The K sampled futures of every agent scored against the goal map and ranked, best first (ynet_score_rank_samples; the
-    samples of utils/evaluate.py:229-266, (x, y) as `sampling` returns them, utils/image_utils.py:110-135).
-    prob [B, n_wp, H, W] = sigmoid_temp(...), waypoint_samples [K, B, n_wp, 2], trajs [K, B, pred_len, 2], all contiguous fp32, K <= 64.
-    score_k = sum over the way-points of log(prob at the sampled pixel + 1e-12), in fp32.
-    -> (ranked [B, K, pred_len, 2] = trajs by descending score / resize_factor (original-image pixels), ranked_goals [B, K, n_wp, 2],
-        score_sorted [B, K], order [B, K] int32: the sample index of every row; equal scores keep the lower index first).
-    Not differentiable.  A sample outside the map raises (the call waits for its launch to learn that)."""
+def _score_rank(name: str, prob, waypoint_samples, trajs, resize_factor, with_rows: bool, out_row=None):
+    """The body of score_rank_samples and (``with_rows``) score_rank_samples_rows; ``name`` is the caller's, for the messages."""
     for t, what in ((prob, "prob"), (waypoint_samples, "waypoint_samples"), (trajs, "trajs")):
-        _need_gpu(t, "score_rank_samples " + what)
+        _need_gpu(t, f"{name} {what}")
     if prob.dim() != 4 or waypoint_samples.dim() != 4 or trajs.dim() != 4:
-        raise ValueError("score_rank_samples: expected prob [B, n_wp, H, W], waypoint_samples [K, B, n_wp, 2] and trajs [K, B, pred_len, 2]")
+        raise ValueError(f"{name}: expected prob [B, n_wp, H, W], waypoint_samples [K, B, n_wp, 2] and trajs [K, B, pred_len, 2]")
     B, n_wp, H, W = prob.shape
     K, pred_len = waypoint_samples.shape[0], trajs.shape[2]
     if tuple(waypoint_samples.shape) != (K, B, n_wp, 2) or tuple(trajs.shape) != (K, B, pred_len, 2):
-        raise ValueError(f"score_rank_samples: waypoint_samples {tuple(waypoint_samples.shape)} / trajs {tuple(trajs.shape)} do not go with "
+        raise ValueError(f"{name}: waypoint_samples {tuple(waypoint_samples.shape)} / trajs {tuple(trajs.shape)} do not go with "
                          f"prob {tuple(prob.shape)} (expected [K, {B}, {n_wp}, 2] and [K, {B}, pred_len, 2])")
     for t, what in ((prob, "prob"), (waypoint_samples, "waypoint_samples"), (trajs, "trajs")):
         if not t.is_contiguous():
-            raise ValueError(f"score_rank_samples: {what} is not contiguous (strides {t.stride()}); the kernel addresses dense arrays")
+            raise ValueError(f"{name}: {what} is not contiguous (strides {t.stride()}); the kernel addresses dense arrays")
     if not float(resize_factor) > 0:
-        raise ValueError("score_rank_samples: the resize factor must be positive")
+        raise ValueError(f"{name}: the resize factor must be positive")
     dev = prob.device
+    rows = None
+    if with_rows:
+        if not (torch.is_tensor(out_row) and out_row.is_cuda):
+            check_row_permutation(out_row, B)
+        rows, _ = _row_index(out_row, dev, f"{name} out_row")
+        if rows.numel() != B:
+            raise ValueError(f"{name}: out_row holds {rows.numel()} entries for {B} agents")
     with torch.no_grad():
         prob, waypoint_samples, trajs = prob.detach(), waypoint_samples.detach(), trajs.detach()
         ranked = torch.empty((B, K, pred_len, 2), device=dev, dtype=torch.float32)
@@ -2732,14 +2731,29 @@ def score_rank_samples(prob: torch.Tensor, waypoint_samples: torch.Tensor, trajs
         # x / resize_factor as torch divides a float tensor by a Python number on the device: the reciprocal taken in double, rounded to fp32, one product
         inv = float(np.float32(1.0 / float(resize_factor)))
         lib = _lib()
-        L.check(lib.ynet_score_rank_samples(prob.data_ptr(), waypoint_samples.data_ptr(), trajs.data_ptr(), B, K, n_wp, pred_len, H, W, inv,
-                                            score.data_ptr(), order.data_ptr(), ranked.data_ptr(), ranked_goals.data_ptr(), st.data_ptr(),
-                                            _stream()), lib)
-        if int(st.item()) != 0:
+        tail = (B, K, n_wp, pred_len, H, W, inv, score.data_ptr(), order.data_ptr(), ranked.data_ptr(), ranked_goals.data_ptr(), st.data_ptr(),
+                _stream())
+        if rows is None:
+            L.check(lib.ynet_score_rank_samples(prob.data_ptr(), waypoint_samples.data_ptr(), trajs.data_ptr(), *tail), lib)
+        else:
+            L.check(lib.ynet_score_rank_samples_rows(prob.data_ptr(), waypoint_samples.data_ptr(), trajs.data_ptr(), rows.data_ptr(), *tail), lib)
+        code = int(st.item())
+        if code != 0:
             st.zero_()
-            raise RuntimeError(f"score_rank_samples: a sample lies outside the {H}x{W} map")
+            raise RuntimeError(f"{name}: a sample lies outside the {H}x{W} map" if code == 1 else
+                               f"{name}: out_row names a row outside 0 .. {B - 1}")
     return ranked, ranked_goals, score, order
 
+
+def score_rank_samples(prob: torch.Tensor, waypoint_samples: torch.Tensor, trajs: torch.Tensor, resize_factor: float):
+    """The K sampled futures of every agent scored against the goal map and ranked, best first (ynet_score_rank_samples; the
+    samples of utils/evaluate.py:229-266, (x, y) as `sampling` returns them, utils/image_utils.py:110-135).
+    prob [B, n_wp, H, W] = sigmoid_temp(...), waypoint_samples [K, B, n_wp, 2], trajs [K, B, pred_len, 2], all contiguous fp32, K <= 64.
+    score_k = sum over the way-points of log(prob at the sampled pixel + 1e-12), in fp32.
+    -> (ranked [B, K, pred_len, 2] = trajs by descending score / resize_factor (original-image pixels), ranked_goals [B, K, n_wp, 2],
+        score_sorted [B, K], order [B, K] int32: the sample index of every row; equal scores keep the lower index first).
+    Not differentiable.  A sample outside the map raises (the call waits for its launch to learn that)."""
+    return _score_rank("score_rank_samples", prob, waypoint_samples, trajs, resize_factor, False)
 
 
 def _row_index(idx, dev, what: str):
@@ -2772,44 +2786,7 @@ def score_rank_samples_rows(prob: torch.Tensor, waypoint_samples: torch.Tensor, 
     row out_row[b] of the results, so they come back in the caller's order from the ranking launch itself.  out_row: a permutation of
     0 .. B - 1, as a host array / list (checked here) or a device int32 tensor (checked by the kernel: an entry out of range writes
     nothing and raises).  Operands, rules and results otherwise as score_rank_samples."""
-    for t, what in ((prob, "prob"), (waypoint_samples, "waypoint_samples"), (trajs, "trajs")):
-        _need_gpu(t, "score_rank_samples_rows " + what)
-    if prob.dim() != 4 or waypoint_samples.dim() != 4 or trajs.dim() != 4:
-        raise ValueError("score_rank_samples_rows: expected prob [B, n_wp, H, W], waypoint_samples [K, B, n_wp, 2] and trajs [K, B, pred_len, 2]")
-    B, n_wp, H, W = prob.shape
-    K, pred_len = waypoint_samples.shape[0], trajs.shape[2]
-    if tuple(waypoint_samples.shape) != (K, B, n_wp, 2) or tuple(trajs.shape) != (K, B, pred_len, 2):
-        raise ValueError(f"score_rank_samples_rows: waypoint_samples {tuple(waypoint_samples.shape)} / trajs {tuple(trajs.shape)} do not go "
-                         f"with prob {tuple(prob.shape)} (expected [K, {B}, {n_wp}, 2] and [K, {B}, pred_len, 2])")
-    for t, what in ((prob, "prob"), (waypoint_samples, "waypoint_samples"), (trajs, "trajs")):
-        if not t.is_contiguous():
-            raise ValueError(f"score_rank_samples_rows: {what} is not contiguous (strides {t.stride()}); the kernel addresses dense arrays")
-    if not float(resize_factor) > 0:
-        raise ValueError("score_rank_samples_rows: the resize factor must be positive")
-    dev = prob.device
-    if not (torch.is_tensor(out_row) and out_row.is_cuda):
-        check_row_permutation(out_row, B)
-    rows, _ = _row_index(out_row, dev, "score_rank_samples_rows out_row")
-    if rows.numel() != B:
-        raise ValueError(f"score_rank_samples_rows: out_row holds {rows.numel()} entries for {B} agents")
-    with torch.no_grad():
-        prob, waypoint_samples, trajs = prob.detach(), waypoint_samples.detach(), trajs.detach()
-        ranked = torch.empty((B, K, pred_len, 2), device=dev, dtype=torch.float32)
-        ranked_goals = torch.empty((B, K, n_wp, 2), device=dev, dtype=torch.float32)
-        score = torch.empty((B, K), device=dev, dtype=torch.float32)
-        order = torch.empty((B, K), device=dev, dtype=torch.int32)
-        st = _status_flag(_score_status, dev)
-        inv = float(np.float32(1.0 / float(resize_factor)))      # (as score_rank_samples)
-        lib = _lib()
-        L.check(lib.ynet_score_rank_samples_rows(prob.data_ptr(), waypoint_samples.data_ptr(), trajs.data_ptr(), rows.data_ptr(), B, K, n_wp,
-                                                 pred_len, H, W, inv, score.data_ptr(), order.data_ptr(), ranked.data_ptr(),
-                                                 ranked_goals.data_ptr(), st.data_ptr(), _stream()), lib)
-        code = int(st.item())
-        if code != 0:
-            st.zero_()
-            raise RuntimeError(f"score_rank_samples_rows: a sample lies outside the {H}x{W} map" if code == 1 else
-                               f"score_rank_samples_rows: out_row names a row outside 0 .. {B - 1}")
-    return ranked, ranked_goals, score, order
+    return _score_rank("score_rank_samples_rows", prob, waypoint_samples, trajs, resize_factor, True, out_row)
 
 
 _gather_status = {}

@@ -65,34 +65,67 @@ def _decoder_passes(model, features, waypoint_samples, input_template, n_local, 
     return torch.cat(trajs_samples)
 
 
+def _goal_maps(model, pred_features, scene_image, observed, input_template, waypoints, obs_len, temperature, network):
+    """The front half of a chunk (utils/evaluate.py:109-131): the observed coordinates [n, obs_len, 2] (host or device tensor) of
+    the agents of one scene [1, C, H, W] -> (encoder features, pred_goal_map [n, pred_len, H, W], wp_sigmoid = sigmoid(pred_goal_map[:,
+    waypoints] / T): channel gather + scale + sigmoid in one pass).  `pred_features`: model.pred_features, or a StyleBank's bound
+    to the row bounds of a style-sorted chunk."""
+    _, _, H, W = scene_image.shape
+    observed_map = gather_patches(input_template, observed.reshape(-1, 2), H, W).view(-1, obs_len, H, W)
+    if network == "embed":      # utils/evaluate.py:119-121
+        observed_map = model.motion_embedding(observed_map)
+    features = pred_features(scene_image.expand(len(observed), -1, -1, -1), observed_map)
+    pred_goal_map = model.pred_goal(features)
+    return features, pred_goal_map, ops.sigmoid_temp(pred_goal_map, waypoints, temperature)
+
+
+def _draw_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, n_goal, n_traj, obs_len, device, use_TTST=False, use_CWS=False,
+                    rel_thresh=0.002, CWS_params=None, forced_goals=None, forced_ttst_samples=None, seeds=None):
+    """The goal / way-point draws of one chunk (utils/evaluate.py:109-224) -> [K, n, n_wp, 2].  The order of the draws is the contract:
+    the goal draw first (under TTST the 10000-sample draw, then np.random.choice per person), then the way-point draw (under CWS in the
+    reference's order).  `forced_goals` [n_goal, n, 1, 2] replaces the goal draw, `forced_ttst_samples` [10000, n, 1, 2] the TTST draw.
+    `seeds`: None -- each draw takes its seed from torch's CPU generator -- or the device int64 tensor of the captured sweep with one
+    seed per draw (no TTST, no CWS: those draw on the host as well).  `batch` [n, >= obs_len, 2] is read by CWS alone."""
+    if forced_goals is not None:
+        goal_samples = forced_goals.to(device)
+    elif use_TTST:
+        draw = None if forced_ttst_samples is None else forced_ttst_samples.to(device)
+        goal_samples = ttst_goals(model, wp_sigmoid[:, -1:], pred_goal_map[:, waypoints[-1:]], n_goal, rel_thresh, draw)
+    else:
+        goal_samples = sampling(wp_sigmoid[:, -1:], num_samples=n_goal, seed=None if seeds is None else seeds[0:1]).permute(2, 0, 1, 3)
+    if len(waypoints) == 1:
+        return goal_samples
+    if use_CWS:
+        last_observed = batch[:, obs_len - 1].to(device)
+        return cws_waypoints(model, wp_sigmoid, goal_samples, last_observed, n_goal, n_traj,
+                             CWS_params["sigma_factor"], CWS_params["ratio"], CWS_params["rot"])
+    waypoint_samples = sampling(wp_sigmoid[:, :-1], num_samples=n_goal * n_traj,
+                                seed=None if seeds is None else seeds[1:2]).permute(2, 0, 1, 3)
+    return torch.cat([waypoint_samples, goal_samples.repeat(n_traj, 1, 1, 1)], dim=2)
+
+
+def _best_of_k(gt_future, gt_goal, trajs_samples, waypoint_samples, resize_factor):
+    """ADE / FDE of the K samples against the ground truth (utils/evaluate.py:268-291) -> (ade [n], fde [n]: the best of the K,
+    ade_batch [K, n]: every sample's)"""
+    ade_batch = ((((gt_future - trajs_samples) / resize_factor) ** 2).sum(dim=3) ** 0.5).mean(dim=2)
+    fde_batch = ((((gt_goal - waypoint_samples[:, :, -1:]) / resize_factor) ** 2).sum(dim=3) ** 0.5)
+    return ade_batch.min(dim=0)[0], fde_batch.min(dim=0)[0][:, 0], ade_batch
+
+
 def _plain_sweep(model, coords, scene_image, input_template, waypoints, n_goal, n_traj, obs_len, temperature, resize_factor, network,
                  max_effective_batch, device, seeds=None):
     """One batch of the sweep as every shipped configuration runs it (no TTST, no CWS, nothing forced, utils/evaluate.py:109-291):
     encoder + goal decoder, sigmoid(x / T), goal and way-point draws, the K decoder passes, best-of-K ADE / FDE.  `coords`
-    [n_local, obs + pred, 2]: host tensor (eager: window checks on the host) or device tensor (captured sweep).  `seeds`: None --
-    each draw takes its seed from torch's CPU generator, in this order -- or a device int64 tensor with one seed per draw.
-    -> (ade [n_local], fde [n_local])"""
+    [n_local, obs + pred, 2]: host tensor (eager: window checks on the host) or device tensor (captured sweep).  `seeds`: as for
+    _draw_waypoints.  -> (ade [n_local], fde [n_local])"""
     _, _, H, W = scene_image.shape
     n_local, n_wp = coords.shape[0], len(waypoints)
-    observed_map = gather_patches(input_template, coords[:, :obs_len].reshape(-1, 2), H, W).view(-1, obs_len, H, W)
     gt_future = coords[:, obs_len:].to(device)
-    if network == "embed":      # utils/evaluate.py:119-121
-        observed_map = model.motion_embedding(observed_map)
-    features = model.pred_features(scene_image.expand(n_local, -1, -1, -1), observed_map)
-    pred_goal_map = model.pred_goal(features)
-    wp_sigmoid = ops.sigmoid_temp(pred_goal_map, waypoints, temperature)
-    goal_samples = sampling(wp_sigmoid[:, -1:], num_samples=n_goal, seed=None if seeds is None else seeds[0:1]).permute(2, 0, 1, 3)
-    if n_wp > 1:
-        waypoint_samples = sampling(wp_sigmoid[:, :-1], num_samples=n_goal * n_traj,
-                                    seed=None if seeds is None else seeds[1:2]).permute(2, 0, 1, 3)
-        waypoint_samples = torch.cat([waypoint_samples, goal_samples.repeat(n_traj, 1, 1, 1)], dim=2)
-    else:
-        waypoint_samples = goal_samples
+    features, pred_goal_map, wp_sigmoid = _goal_maps(model, model.pred_features, scene_image, coords[:, :obs_len], input_template, waypoints,
+                                                     obs_len, temperature, network)
+    waypoint_samples = _draw_waypoints(model, wp_sigmoid, pred_goal_map, coords, waypoints, n_goal, n_traj, obs_len, device, seeds=seeds)
     trajs_samples = _decoder_passes(model, features, waypoint_samples, input_template, n_local, n_wp, H, W, max_effective_batch, device)
-    gt_goal = gt_future[:, -1:]
-    ade_batch = ((((gt_future - trajs_samples) / resize_factor) ** 2).sum(dim=3) ** 0.5).mean(dim=2)
-    fde_batch = ((((gt_goal - waypoint_samples[:, :, -1:]) / resize_factor) ** 2).sum(dim=3) ** 0.5)
-    return ade_batch.min(dim=0)[0], fde_batch.min(dim=0)[0][:, 0]
+    return _best_of_k(gt_future, gt_future[:, -1:], trajs_samples, waypoint_samples, resize_factor)[:2]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -272,37 +305,20 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                                 entry.seen = True
                             ade, fde = body(batch, scene_image, None)
                     elif n_local > 0:
-                        observed_map = gather_patches(input_template, batch[:, :obs_len].reshape(-1, 2), H, W).view(-1, obs_len, H, W)
                         gt_future = batch[:, obs_len:].to(device)
-                        if network == "embed":      # utils/evaluate.py:119-121
-                            observed_map = model.motion_embedding(observed_map)
-                        features = model.pred_features(scene_image.expand(n_local, -1, -1, -1), observed_map)
-                        pred_goal_map = model.pred_goal(features)
-                        # sigmoid(pred_goal_map[:, waypoints] / T): channel gather + scale + sigmoid in one pass
-                        wp_sigmoid = ops.sigmoid_temp(pred_goal_map, waypoints, temperature)
+                        features, pred_goal_map, wp_sigmoid = _goal_maps(model, model.pred_features, scene_image, batch[:, :obs_len],
+                                                                         input_template, waypoints, obs_len, temperature, network)
                         if return_likelihood:      # every step's plane against its ground truth, in resized pixels: one launch
                             like = ops.map_likelihood(pred_goal_map, gt_future, temperature)
 
                         if forced_samples is not None:
                             waypoint_samples = forced_samples[b][:, lo:lo + n_local].to(device)
                         else:
-                            if forced_goals is not None:
-                                goal_samples = forced_goals[b][:, lo:lo + n_local].to(device)
-                            elif use_TTST:
-                                draw = None if forced_ttst_samples is None else forced_ttst_samples[b][:, lo:lo + n_local].to(device)
-                                goal_samples = ttst_goals(model, wp_sigmoid[:, -1:], pred_goal_map[:, waypoints[-1:]], n_goal,
-                                                          rel_thresh, draw)
-                            else:
-                                goal_samples = sampling(wp_sigmoid[:, -1:], num_samples=n_goal).permute(2, 0, 1, 3)
-                            if use_CWS and n_wp > 1:
-                                last_observed = batch[:, obs_len - 1].to(device)
-                                waypoint_samples = cws_waypoints(model, wp_sigmoid, goal_samples, last_observed, n_goal, n_traj,
-                                                                 CWS_params["sigma_factor"], CWS_params["ratio"], CWS_params["rot"])
-                            elif n_wp > 1:
-                                waypoint_samples = sampling(wp_sigmoid[:, :-1], num_samples=n_goal * n_traj).permute(2, 0, 1, 3)
-                                waypoint_samples = torch.cat([waypoint_samples, goal_samples.repeat(n_traj, 1, 1, 1)], dim=2)
-                            else:
-                                waypoint_samples = goal_samples
+                            def mine(forced):      # this rank's rows of a forced draw of the batch
+                                return None if forced is None else forced[b][:, lo:lo + n_local]
+                            waypoint_samples = _draw_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, n_goal, n_traj, obs_len, device,
+                                                               use_TTST, use_CWS, rel_thresh, CWS_params, mine(forced_goals),
+                                                               mine(forced_ttst_samples))
 
                         if return_samples:
                             trajs_dict["goal_map"].append(pred_goal_map.cpu().numpy())
@@ -315,16 +331,13 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                         if dataset_name == "eth":
                             waypoint_samples = image2world(waypoint_samples, scene_id, homo_mat, resize_factor)
                             gt_future = image2world(gt_future, scene_id, homo_mat, resize_factor)
-                        ade_batch = ((((gt_future - trajs_samples) / resize_factor) ** 2).sum(dim=3) ** 0.5).mean(dim=2)
-                        fde_batch = ((((gt_goal - waypoint_samples[:, :, -1:]) / resize_factor) ** 2).sum(dim=3) ** 0.5)
+                        ade, fde, ade_batch = _best_of_k(gt_future, gt_goal, trajs_samples, waypoint_samples, resize_factor)
                         if return_preds:
                             if b == 0:
                                 trajs_dict["groundtruth"].append(trajectory.cpu().numpy() / resize_factor)
                             best = ade_batch.argmin(dim=0)
                             trajs_dict["prediction"].append(
                                 (trajs_samples[best, torch.arange(trajs_samples.shape[1], device=device)] / resize_factor).cpu().numpy())
-                        ade = ade_batch.min(dim=0)[0]
-                        fde = fde_batch.min(dim=0)[0][:, 0]
                     else:
                         ade = fde = torch.zeros(0, device=device)
                         if return_likelihood:

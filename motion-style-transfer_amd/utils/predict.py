@@ -13,44 +13,137 @@ that batch.  Nothing is captured into a hipGraph here; evaluate()'s captured-swe
 ``predict_styles`` is predict() for a scene whose agents wear different styles: one frozen model, the adapter sets of a
 models.style_bank.StyleBank, one call.
 """
+import functools
 import inspect
 
 import numpy as np
 import torch
 
 from .. import ops
-from .evaluate import _decoder_passes, cws_waypoints, ttst_goals
-from .image_utils import gather_patches, sampling, swap_pavement_terrain
+from .evaluate import _decoder_passes, _draw_waypoints, _goal_maps      # (evaluate()'s own steps, not copies)
+from .image_utils import swap_pavement_terrain
 
 MAX_SAMPLES = 64      # ynet_score_rank_samples ranks the samples of an agent on the lanes of one wavefront
 
 
-def _observed_tensor(observed, obs_len):
+def _validated(name, observed, scene_image, waypoints, n_goal, n_traj, obs_len, resize_factor, use_CWS, CWS_params, batch_size, forced_samples,
+               bank=None, style=None):
+    """Everything `name` (predict / predict_styles) refuses before the device is touched -> (observed as a float tensor [N, obs_len, 2],
+    waypoints, n_goal, n_traj, obs_len, and with a ``bank`` the style index [N] of every agent)"""
+    waypoints = list(waypoints)
+    n_wp = len(waypoints)
+    n_goal, n_traj, obs_len = int(n_goal), int(n_traj), int(obs_len)
+    K = n_goal * n_traj
+    if n_goal < 1 or n_traj < 1:
+        raise ValueError(f"{name}: n_goal = {n_goal}, n_traj = {n_traj}: at least one sample per agent is needed")
+    if K > MAX_SAMPLES:
+        raise ValueError(f"{name}: n_goal * n_traj = {K} samples per agent; the ranking kernel takes up to {MAX_SAMPLES}")
+    if n_wp < 1:
+        raise ValueError(f"{name}: no way-points")
+    if use_CWS and n_wp > 1 and CWS_params is None:
+        raise ValueError(f"{name}: use_CWS needs CWS_params (sigma_factor, ratio, rot)")
+    if not float(resize_factor) > 0:
+        raise ValueError(f"{name}: resize_factor must be positive")
+    if batch_size is not None and int(batch_size) < 1:
+        raise ValueError(f"{name}: batch_size must be positive")
     obs = observed.detach() if torch.is_tensor(observed) else torch.from_numpy(np.ascontiguousarray(np.asarray(observed, dtype=np.float32)))
     if obs.dim() != 3 or obs.shape[2] != 2:
-        raise ValueError(f"predict: observed must be [N, obs_len, 2] (x, y) in resized pixel coordinates, got {tuple(obs.shape)}")
+        raise ValueError(f"{name}: observed must be [N, obs_len, 2] (x, y) in resized pixel coordinates, got {tuple(obs.shape)}")
     if obs.shape[1] != obs_len:
-        raise ValueError(f"predict: observed holds {obs.shape[1]} steps per agent, obs_len is {obs_len}: pass exactly the observed steps "
+        raise ValueError(f"{name}: observed holds {obs.shape[1]} steps per agent, obs_len is {obs_len}: pass exactly the observed steps "
                          f"(a longer track is never cut silently)")
-    return obs.float()
+    if not torch.is_tensor(scene_image) or scene_image.dim() != 3:
+        raise ValueError(f"{name}: scene_image must be the tensor [C, H, W] of one scene")
+    N = obs.shape[0]
+    if N == 0:
+        raise ValueError(f"{name}: no agents (observed is empty)")
+    style_index = None
+    if bank is not None:
+        style_index = np.asarray(bank.indices(style), dtype=np.int64)      # (an unknown style is refused here)
+        if style_index.shape != (N,):
+            raise ValueError(f"{name}: {style_index.size} styles for {N} agents: one name or index per agent is needed")
+    if torch.is_tensor(forced_samples) and tuple(forced_samples.shape) != (K, N, n_wp, 2):
+        raise ValueError(f"{name}: forced_samples {tuple(forced_samples.shape)}, expected {(K, N, n_wp, 2)}"
+                         + ("" if bank is None else " in the caller's order"))
+    return obs.float(), waypoints, n_goal, n_traj, obs_len, style_index
 
 
-def _draw_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, n_goal, n_traj, obs_len, use_TTST, use_CWS, rel_thresh, CWS_params,
-                    device):
-    """The goal / way-point draws of one chunk, in evaluate()'s order (utils/evaluate.py:109-224) -> [K, n, n_wp, 2]"""
-    n_wp = len(waypoints)
-    if use_TTST:
-        goal_samples = ttst_goals(model, wp_sigmoid[:, -1:], pred_goal_map[:, waypoints[-1:]], n_goal, rel_thresh)
-    else:
-        goal_samples = sampling(wp_sigmoid[:, -1:], num_samples=n_goal).permute(2, 0, 1, 3)
-    if use_CWS and n_wp > 1:
-        last_observed = batch[:, obs_len - 1].to(device)
-        return cws_waypoints(model, wp_sigmoid, goal_samples, last_observed, n_goal, n_traj,
-                             CWS_params["sigma_factor"], CWS_params["ratio"], CWS_params["rot"])
-    if n_wp > 1:
-        waypoint_samples = sampling(wp_sigmoid[:, :-1], num_samples=n_goal * n_traj).permute(2, 0, 1, 3)
-        return torch.cat([waypoint_samples, goal_samples.repeat(n_traj, 1, 1, 1)], dim=2)
-    return goal_samples
+def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
+              use_TTST, use_CWS, rel_thresh, CWS_params, network, swap_semantic, batch_size, max_effective_batch, forced_samples, return_maps,
+              return_entropy):
+    """The one body of predict(), predict_with_entropy() and predict_styles(), on arguments that went through _validated.
+    refresh()          packs the filters the chunks will read, on the caller's stream, before the decoder passes fan out over two (see
+                       evaluate()): ops.refresh_filters(model), or a StyleBank's refresh() for its shadows and the shared layers
+    chunk_plan(b, n)   for the n agents from b on -> (perm, pred_features): ``perm`` None, or the order the chunk runs in (row j of the
+                       sweep is the chunk's agent perm[j]); ``pred_features`` the feature function of the chunk in that order
+    When ``perm`` is the identity (or None) nothing is gathered and the ranking launch writes row b at row b; otherwise the observed
+    steps and forced samples are gathered into the sweep's order, the ranking launch writes every agent's results at its row of the
+    caller's order, and the maps, when asked for, are gathered back."""
+    n_wp, K = len(waypoints), n_goal * n_traj
+    N = obs.shape[0]
+    step = N if batch_size is None else int(batch_size)
+    device = next(model.parameters()).device
+    was_training = model.training
+    model.eval()
+    out = {k: [] for k in ["trajectories", "waypoints", "scores", "order"] + (["goal_map", "goal_sigmoid_map"] if return_maps else [])
+           + (["entropy"] if return_entropy else [])}
+    try:
+        with torch.no_grad():
+            refresh()
+            scene = model.segmentation(scene_image.to(device).unsqueeze(0))
+            scene = model.adapt_semantic(scene)
+            if swap_semantic:
+                scene = swap_pavement_terrain(scene)
+            if network == "embed":
+                scene = model.scene_embedding(scene)
+            _, _, H, W = scene.shape
+            for b in range(0, N, step):
+                batch = obs[b:b + step]
+                n = len(batch)
+                perm, pred_features = chunk_plan(b, n)
+                mixed = perm is not None and not np.array_equal(perm, np.arange(n))
+                if mixed:
+                    perm_dev = torch.from_numpy(perm.astype(np.int32)).to(device)
+                    batch = ops.gather_rows(batch.to(device).contiguous(), perm_dev)
+                features, pred_goal_map, wp_sigmoid = _goal_maps(model, pred_features, scene, batch, input_template, waypoints, obs_len,
+                                                                 temperature, network)
+
+                if forced_samples is not None:
+                    forced = forced_samples[:, b:b + n] if torch.is_tensor(forced_samples) else forced_samples[b]
+                    waypoint_samples = forced.to(device)
+                    if tuple(waypoint_samples.shape) != (K, n, n_wp, 2):
+                        raise ValueError(f"{name}: forced samples {tuple(waypoint_samples.shape)} for the chunk at {b}, expected {(K, n, n_wp, 2)}")
+                    if mixed:      # a row gather inside each of the K slabs
+                        slab_rows = (torch.arange(K, device=device, dtype=torch.int32)[:, None] * n + perm_dev[None]).reshape(-1)
+                        waypoint_samples = ops.gather_rows(waypoint_samples.float().contiguous().view(K * n, n_wp, 2), slab_rows).view(K, n, n_wp, 2)
+                else:      # (over the chunk as it runs: draw row j belongs to sweep row j)
+                    waypoint_samples = _draw_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, n_goal, n_traj, obs_len, device,
+                                                       use_TTST, use_CWS, rel_thresh, CWS_params)
+                waypoint_samples = waypoint_samples.float().contiguous()
+
+                if return_maps:
+                    maps = {"goal_map": pred_goal_map, "goal_sigmoid_map": model.sigmoid(pred_goal_map / temperature)}
+                    if mixed:
+                        back = torch.from_numpy(np.argsort(perm).astype(np.int32)).to(device)      # caller row i <- sweep row back[i]
+                        maps = {k: ops.gather_rows(v.contiguous(), back) for k, v in maps.items()}
+                    for k, v in maps.items():
+                        out[k].append(v)
+                if return_entropy:
+                    out["entropy"].append(ops.map_likelihood(pred_goal_map, None, temperature, want=("entropy",))["entropy"])
+
+                trajs_samples = _decoder_passes(model, features, waypoint_samples, input_template, n, n_wp, H, W, max_effective_batch, device)
+                ranking = (wp_sigmoid, waypoint_samples, trajs_samples.contiguous(), resize_factor)
+                ranked, ranked_goals, score, order = ops.score_rank_samples_rows(*ranking, perm) if mixed else ops.score_rank_samples(*ranking)
+                out["trajectories"].append(ranked)
+                out["waypoints"].append(ranked_goals)
+                out["scores"].append(score)
+                out["order"].append(order)
+                ops.check_patch_status()      # (the ranking call waited for the chunk: a window that left the template raises here)
+                if perm is not None:
+                    ops.check_gather_status()
+    finally:
+        model.train(was_training)
+    return {k: (v[0] if len(v) == 1 else torch.cat(v)) for k, v in out.items()}
 
 
 def predict(model, scene_image, observed, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
@@ -83,85 +176,14 @@ def predict_with_entropy(*args, **kwargs):
 
 
 def _predict(return_entropy, model, scene_image, observed, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
-             use_TTST, use_CWS, rel_thresh, CWS_params, network, swap_semantic, batch_size, max_effective_batch, forced_samples, return_maps):
-    """The body of predict() / predict_with_entropy()"""
-    waypoints = list(waypoints)
-    n_wp = len(waypoints)
-    n_goal, n_traj, obs_len = int(n_goal), int(n_traj), int(obs_len)
-    K = n_goal * n_traj
-    if n_goal < 1 or n_traj < 1:
-        raise ValueError(f"predict: n_goal = {n_goal}, n_traj = {n_traj}: at least one sample per agent is needed")
-    if K > MAX_SAMPLES:
-        raise ValueError(f"predict: n_goal * n_traj = {K} samples per agent; the ranking kernel takes up to {MAX_SAMPLES}")
-    if n_wp < 1:
-        raise ValueError("predict: no way-points")
-    if use_CWS and n_wp > 1 and CWS_params is None:
-        raise ValueError("predict: use_CWS needs CWS_params (sigma_factor, ratio, rot)")
-    if not float(resize_factor) > 0:
-        raise ValueError("predict: resize_factor must be positive")
-    if batch_size is not None and int(batch_size) < 1:
-        raise ValueError("predict: batch_size must be positive")
-    obs = _observed_tensor(observed, obs_len)
-    if not torch.is_tensor(scene_image) or scene_image.dim() != 3:
-        raise ValueError("predict: scene_image must be the tensor [C, H, W] of one scene")
-    N = obs.shape[0]
-    if N == 0:
-        raise ValueError("predict: no agents (observed is empty)")
-    if torch.is_tensor(forced_samples) and tuple(forced_samples.shape) != (K, N, n_wp, 2):
-        raise ValueError(f"predict: forced_samples {tuple(forced_samples.shape)}, expected {(K, N, n_wp, 2)}")
-    step = N if batch_size is None else int(batch_size)
-    device = next(model.parameters()).device
-    was_training = model.training
-    model.eval()
-    out = {k: [] for k in ["trajectories", "waypoints", "scores", "order"] + (["goal_map", "goal_sigmoid_map"] if return_maps else [])
-           + (["entropy"] if return_entropy else [])}
-    try:
-        with torch.no_grad():
-            ops.refresh_filters(model)      # on the caller's stream, before the decoder passes fan out over two (see evaluate())
-            scene = model.segmentation(scene_image.to(device).unsqueeze(0))
-            scene = model.adapt_semantic(scene)
-            if swap_semantic:
-                scene = swap_pavement_terrain(scene)
-            if network == "embed":
-                scene = model.scene_embedding(scene)
-            _, _, H, W = scene.shape
-            for b in range(0, N, step):
-                batch = obs[b:b + step]
-                n = len(batch)
-                observed_map = gather_patches(input_template, batch.reshape(-1, 2), H, W).view(-1, obs_len, H, W)
-                if network == "embed":
-                    observed_map = model.motion_embedding(observed_map)
-                features = model.pred_features(scene.expand(n, -1, -1, -1), observed_map)
-                pred_goal_map = model.pred_goal(features)
-                wp_sigmoid = ops.sigmoid_temp(pred_goal_map, waypoints, temperature)
-
-                if forced_samples is not None:
-                    forced = forced_samples[:, b:b + n] if torch.is_tensor(forced_samples) else forced_samples[b]
-                    waypoint_samples = forced.to(device)
-                    if tuple(waypoint_samples.shape) != (K, n, n_wp, 2):
-                        raise ValueError(f"predict: forced samples {tuple(waypoint_samples.shape)} for the chunk at {b}, expected {(K, n, n_wp, 2)}")
-                else:
-                    waypoint_samples = _draw_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, n_goal, n_traj, obs_len, use_TTST,
-                                                       use_CWS, rel_thresh, CWS_params, device)
-                waypoint_samples = waypoint_samples.float().contiguous()
-
-                if return_maps:
-                    out["goal_map"].append(pred_goal_map)
-                    out["goal_sigmoid_map"].append(model.sigmoid(pred_goal_map / temperature))
-                if return_entropy:
-                    out["entropy"].append(ops.map_likelihood(pred_goal_map, None, temperature, want=("entropy",))["entropy"])
-
-                trajs_samples = _decoder_passes(model, features, waypoint_samples, input_template, n, n_wp, H, W, max_effective_batch, device)
-                ranked, ranked_goals, score, order = ops.score_rank_samples(wp_sigmoid, waypoint_samples, trajs_samples.contiguous(),
-                                                                           resize_factor)
-                out["trajectories"].append(ranked)
-                out["waypoints"].append(ranked_goals)
-                out["scores"].append(score)
-                out["order"].append(order)
-                ops.check_patch_status()      # (score_rank_samples waited for the chunk: a window that left the template raises here)
-    finally:
-        model.train(was_training)
-    return {k: (v[0] if len(v) == 1 else torch.cat(v)) for k, v in out.items()}
+             use_TTST, use_CWS, rel_thresh, CWS_params, batch_size, forced_samples, **options):
+    """predict() / predict_with_entropy(): no permutation, the model's own features and filters"""
+    obs, waypoints, n_goal, n_traj, obs_len, _ = _validated("predict", observed, scene_image, waypoints, n_goal, n_traj, obs_len, resize_factor,
+                                                            use_CWS, CWS_params, batch_size, forced_samples)
+    return _forecast("predict", model, lambda: ops.refresh_filters(model), lambda b, n: (None, model.pred_features), scene_image, obs,
+                     input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature, use_TTST=use_TTST, use_CWS=use_CWS,
+                     rel_thresh=rel_thresh, CWS_params=CWS_params, batch_size=batch_size, forced_samples=forced_samples,
+                     return_entropy=return_entropy, **options)
 
 
 _PREDICT_SIGNATURE = inspect.signature(predict)
@@ -188,104 +210,15 @@ def predict_styles(bank, scene_image, observed, style, input_template, waypoints
     order and gathered back into the caller's order (one ynet_gather_rows pass over each map, paid only when the maps are asked for).
     evaluate()'s captured-sweep cache is neither used nor touched; the model's filter caches are not written (StyleBank)."""
     from ..models.style_bank import sort_by_style
-    model = bank.model
-    waypoints = list(waypoints)
-    n_wp = len(waypoints)
-    n_goal, n_traj, obs_len = int(n_goal), int(n_traj), int(obs_len)
-    K = n_goal * n_traj
-    if n_goal < 1 or n_traj < 1:
-        raise ValueError(f"predict_styles: n_goal = {n_goal}, n_traj = {n_traj}: at least one sample per agent is needed")
-    if K > MAX_SAMPLES:
-        raise ValueError(f"predict_styles: n_goal * n_traj = {K} samples per agent; the ranking kernel takes up to {MAX_SAMPLES}")
-    if n_wp < 1:
-        raise ValueError("predict_styles: no way-points")
-    if use_CWS and n_wp > 1 and CWS_params is None:
-        raise ValueError("predict_styles: use_CWS needs CWS_params (sigma_factor, ratio, rot)")
-    if not float(resize_factor) > 0:
-        raise ValueError("predict_styles: resize_factor must be positive")
-    if batch_size is not None and int(batch_size) < 1:
-        raise ValueError("predict_styles: batch_size must be positive")
-    obs = _observed_tensor(observed, obs_len)
-    if not torch.is_tensor(scene_image) or scene_image.dim() != 3:
-        raise ValueError("predict_styles: scene_image must be the tensor [C, H, W] of one scene")
-    N = obs.shape[0]
-    if N == 0:
-        raise ValueError("predict_styles: no agents (observed is empty)")
-    style_index = np.asarray(bank.indices(style), dtype=np.int64)      # (an unknown style is refused here)
-    if style_index.shape != (N,):
-        raise ValueError(f"predict_styles: {style_index.size} styles for {N} agents: one name or index per agent is needed")
-    if torch.is_tensor(forced_samples) and tuple(forced_samples.shape) != (K, N, n_wp, 2):
-        raise ValueError(f"predict_styles: forced_samples {tuple(forced_samples.shape)}, expected {(K, N, n_wp, 2)} in the caller's order")
-    step = N if batch_size is None else int(batch_size)
-    device = next(model.parameters()).device
-    was_training = model.training
-    model.eval()
-    out = {k: [] for k in ["trajectories", "waypoints", "scores", "order"] + (["goal_map", "goal_sigmoid_map"] if return_maps else [])}
-    try:
-        with torch.no_grad():
-            # ops.refresh_filters for the shadows and the shared layers, on the caller's stream, before the decoder passes fan out over two
-            bank.refresh()
-            scene = model.segmentation(scene_image.to(device).unsqueeze(0))
-            scene = model.adapt_semantic(scene)
-            if swap_semantic:
-                scene = swap_pavement_terrain(scene)
-            if network == "embed":
-                scene = model.scene_embedding(scene)
-            _, _, H, W = scene.shape
-            for b in range(0, N, step):
-                batch = obs[b:b + step]
-                n = len(batch)
-                perm, offsets = sort_by_style(style_index[b:b + n], len(bank))
-                mixed = not np.array_equal(perm, np.arange(n))
-                if mixed:
-                    perm_dev = torch.from_numpy(perm.astype(np.int32)).to(device)
-                    batch = ops.gather_rows(batch.to(device).contiguous(), perm_dev)
-                observed_map = gather_patches(input_template, batch.reshape(-1, 2), H, W).view(-1, obs_len, H, W)
-                if network == "embed":
-                    observed_map = model.motion_embedding(observed_map)
-                features = bank.pred_features(scene.expand(n, -1, -1, -1), observed_map, offsets)
-                pred_goal_map = model.pred_goal(features)
-                wp_sigmoid = ops.sigmoid_temp(pred_goal_map, waypoints, temperature)
+    obs, waypoints, n_goal, n_traj, obs_len, style_index = _validated("predict_styles", observed, scene_image, waypoints, n_goal, n_traj, obs_len,
+                                                                      resize_factor, use_CWS, CWS_params, batch_size, forced_samples, bank, style)
 
-                if forced_samples is not None:
-                    forced = forced_samples[:, b:b + n] if torch.is_tensor(forced_samples) else forced_samples[b]
-                    waypoint_samples = forced.to(device)
-                    if tuple(waypoint_samples.shape) != (K, n, n_wp, 2):
-                        raise ValueError(f"predict_styles: forced samples {tuple(waypoint_samples.shape)} for the chunk at {b}, expected {(K, n, n_wp, 2)}")
-                    waypoint_samples = waypoint_samples.float().contiguous()
-                    if mixed:      # a row gather inside each of the K slabs
-                        slab_rows = (torch.arange(K, device=device, dtype=torch.int32)[:, None] * n + perm_dev[None]).reshape(-1)
-                        waypoint_samples = ops.gather_rows(waypoint_samples.view(K * n, n_wp, 2), slab_rows).view(K, n, n_wp, 2)
-                else:
-                    waypoint_samples = _draw_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, n_goal, n_traj, obs_len, use_TTST,
-                                                       use_CWS, rel_thresh, CWS_params, device)
-                waypoint_samples = waypoint_samples.float().contiguous()
+    def chunk_plan(b, n):      # the chunk stable-sorted by style, and the bank's features bound to the sorted chunk's row bounds
+        perm, offsets = sort_by_style(style_index[b:b + n], len(bank))
+        return perm, functools.partial(bank.pred_features, offsets=offsets)
 
-                if return_maps:
-                    sig_map = model.sigmoid(pred_goal_map / temperature)
-                    if mixed:
-                        back = torch.from_numpy(np.argsort(perm).astype(np.int32)).to(device)      # caller row i <- sorted row back[i]
-                        out["goal_map"].append(ops.gather_rows(pred_goal_map.contiguous(), back))
-                        out["goal_sigmoid_map"].append(ops.gather_rows(sig_map.contiguous(), back))
-                    else:
-                        out["goal_map"].append(pred_goal_map)
-                        out["goal_sigmoid_map"].append(sig_map)
-
-                trajs_samples = _decoder_passes(model, features, waypoint_samples, input_template, n, n_wp, H, W, max_effective_batch, device)
-                if mixed:
-                    ranked, ranked_goals, score, order = ops.score_rank_samples_rows(wp_sigmoid, waypoint_samples, trajs_samples.contiguous(),
-                                                                                    resize_factor, perm)
-                else:
-                    ranked, ranked_goals, score, order = ops.score_rank_samples(wp_sigmoid, waypoint_samples, trajs_samples.contiguous(),
-                                                                               resize_factor)
-                out["trajectories"].append(ranked)
-                out["waypoints"].append(ranked_goals)
-                out["scores"].append(score)
-                out["order"].append(order)
-                ops.check_patch_status()      # (the ranking call waited for the chunk)
-                ops.check_gather_status()
-    finally:
-        model.train(was_training)
-    res = {k: (v[0] if len(v) == 1 else torch.cat(v)) for k, v in out.items()}
-    res["style_index"] = torch.from_numpy(style_index).to(device)
+    res = _forecast("predict_styles", bank.model, bank.refresh, chunk_plan, scene_image, obs, input_template, waypoints, n_goal, n_traj, obs_len,
+                    resize_factor, temperature, use_TTST, use_CWS, rel_thresh, CWS_params, network, swap_semantic, batch_size,
+                    max_effective_batch, forced_samples, return_maps, return_entropy=False)
+    res["style_index"] = torch.from_numpy(style_index).to(res["scores"].device)
     return res

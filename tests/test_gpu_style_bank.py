@@ -74,6 +74,20 @@ def test_score_rank_rows_matches_fp64(dev, K, n_wp, B):
         assert np.array_equal(goals.cpu().numpy(), wps.transpose(1, 0, 2, 3)[cols, order_h])
 
 
+@pytest.mark.parametrize("B", C.BS)
+@pytest.mark.parametrize("n_wp", C.NWPS)
+@pytest.mark.parametrize("K", C.KS)
+def test_score_rank_rows_with_the_identity_is_score_rank_bit_for_bit(dev, K, n_wp, B):
+    """The two entries run one body: with out_row = 0 .. B - 1 all four results are equal bit for bit, `order` and its ties included."""
+    ops = pkg("ops")
+    prob, wps, trajs = (torch.from_numpy(a).to(dev) for a in C.make_case(K, n_wp, B))
+    plain = ops.score_rank_samples(prob, wps, trajs, 0.25)
+    rows = ops.score_rank_samples_rows(prob, wps, trajs, 0.25, out_row=torch.arange(B, device=dev, dtype=torch.int32))
+    for name, a, b in zip(("ranked", "ranked_goals", "score", "order"), plain, rows):
+        assert a.dtype == b.dtype and a.shape == b.shape, name
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), name      # (bits: a NaN would not hide a difference, -0 is not +0)
+
+
 def test_score_rank_rows_refusals(dev):
     ops = pkg("ops")
     prob, wps, trajs = (torch.from_numpy(a).to(dev) for a in C.make_case(20, 1, 3))

@@ -86,8 +86,10 @@ def test_predict_signature():
                      max_effective_batch=256, forced_samples=None, return_maps=False)
     # the shared pieces of the sweep are evaluate()'s own, not copies
     ev, iu = pkg("utils.evaluate"), pkg("utils.image_utils")
-    assert P._decoder_passes is ev._decoder_passes and P.ttst_goals is ev.ttst_goals and P.cws_waypoints is ev.cws_waypoints
-    assert P.sampling is iu.sampling and P.gather_patches is iu.gather_patches
+    assert P._decoder_passes is ev._decoder_passes and P._goal_maps is ev._goal_maps and P._draw_waypoints is ev._draw_waypoints
+    assert ev.sampling is iu.sampling and ev.gather_patches is iu.gather_patches
+    for name in ("ttst_goals", "cws_waypoints", "sampling", "gather_patches", "_plain_sweep", "_best_of_k"):      # (reached through those)
+        assert getattr(P, name, getattr(ev, name)) is getattr(ev, name)
     assert list(inspect.signature(pkg("models.trainer").YNetTrainer.predict).parameters) == ["self", "df_obs", "image_path_or_images",
                                                                                               "return_maps"]
 
