@@ -290,7 +290,10 @@ def lora_grad(dw, lora_a, lora_b, scale: float):
 
 
 import os as _os
-import weakref
+
+# the hand-over registries, each made next to its protocol below: those fold_skip_gradients() empties on enter and on exit -- every
+# Handover made without step=False -- and all of them (release_stale_entries)
+from ._handover import ALL as _ALL_REGISTRIES, STEP as _STEP_REGISTRIES, Handover
 
 _conv_ws = {}
 _side_streams = {}
@@ -354,6 +357,12 @@ wino_stats = {"launches": 0}
 _wino_eval_min_hw = 0        # smallest H * W of a map that takes a Winograd launch
 _wino_cat_eval = True        # the concatenated-source / shared-term launches
 _wino_plain_eval = True      # the one-source launches
+
+
+def _wino_eval_gated(srcs, H, W):
+    """Do evaluate()'s development gates (above: under no_grad only) keep this convolution off the Winograd launches?"""
+    return not torch.is_grad_enabled() and (
+        H * W < _wino_eval_min_hw or not (_wino_plain_eval if len(srcs) == 1 and srcs[0][1] in (16, 32) else _wino_cat_eval))
 
 
 def _count_launches(n, slice_form=False):
@@ -665,8 +674,7 @@ def conv2d_raw(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=None, poole
     if not conv_auto:
         return _conv2d_raw_py(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=relu_of, pooled=pooled, bits_out=bits_out, relu_bits=relu_bits, wino=wino,
                               wbits_out=wbits_out, relu_wbits=relu_wbits, pool_code=pool_code, dst_s2d=dst_s2d, info=info)
-    if wino is not None and not torch.is_grad_enabled() and (
-            H * W < _wino_eval_min_hw or not (_wino_plain_eval if len(srcs) == 1 and srcs[0][1] in (16, 32) else _wino_cat_eval)):
+    if wino is not None and _wino_eval_gated(srcs, H, W):
         wino = None
     tag, tk = conv2d_auto_raw(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=relu_of, pooled=pooled, bits_out=bits_out, relu_bits=relu_bits, wino=wino,
                               wbits_out=wbits_out, relu_wbits=relu_wbits, pool_code=pool_code, dst_s2d=dst_s2d)
@@ -695,8 +703,7 @@ def _conv2d_raw_py(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=None, p
     sp, sc, sb = _arrays(srcs)
     if info is not None:
         info["wrote_s2d"] = 0
-    if wino is not None and not torch.is_grad_enabled() and (
-            H * W < _wino_eval_min_hw or not (_wino_plain_eval if len(srcs) == 1 and srcs[0][1] in (16, 32) else _wino_cat_eval)):
+    if wino is not None and _wino_eval_gated(srcs, H, W):
         wino = None
     if bits_out is not None:
         if len(dsts) != 1 or mask is not None or relu_of is not None or pooled is not None or not relu or _bmods(srcs) is not None:
@@ -1112,11 +1119,7 @@ refresh_lora_filters = refresh_filters      # (round-2 name)
 # ``torch.autograd.grad(loss, features[i])`` or ``backward(inputs=...)``, where the pool's backward never runs and
 # a handed-over gradient would be dropped.  The fold is therefore OPT-IN: ``with ops.fold_skip_gradients():`` around
 # forward + backward (utils/train_epoch.py does that); everywhere else autograd sums the gradients itself.
-class _SkipEntry:
-    __slots__ = ("ref", "shape", "stash", "consumed")
-
-
-_skip_registry = {}
+_skip_registry = Handover("skip_registry", step=False)      # pool input x -> stash (the gradients handed over, with their events), consumed (the pool's backward ran)
 skip_fold = False                                                   # switched on by fold_skip_gradients() only
 _skip_fold_allowed = _os.environ.get("YNET_SKIP_FOLD", "1") != "0"      # YNET_SKIP_FOLD=0: never fold (A/B runs)
 
@@ -1137,8 +1140,8 @@ _skip_fold_allowed = _os.environ.get("YNET_SKIP_FOLD", "1") != "0"      # YNET_S
 #   * _Conv2dFn.backward drops its own mask when its dy is registered for ITS y and has not been written since
 #     (an in-place accumulation by the autograd engine bumps the version; a sum into a new tensor has a new address).
 # Masking twice is harmless (idempotent), so every doubt resolves to "mask again".
-_relu_outputs = {}
-_premasked = {}
+_relu_outputs = Handover("relu_outputs")                             # conv output y -> bits, k, wbits (the 1-bit masks its forward launch left)
+_premasked = Handover("premasked", weak=False, version=True)         # gradient dx -> y_ptr (the activation whose ReLU backward dx carries)
 premask = False                                                     # switched on by fold_skip_gradients() only
 premask_stats = {"unmasked_backwards": 0}                           # conv backwards that ran without their own mask (tests)
 _premask_allowed = _os.environ.get("YNET_PREMASK", "1") != "0"          # YNET_PREMASK=0: every conv backward masks itself
@@ -1146,8 +1149,7 @@ _relu_bits_allowed = _os.environ.get("YNET_RELU_BITS", "1") != "0"      # YNET_R
 
 
 def _is_relu_output(t: torch.Tensor) -> bool:
-    e = _relu_outputs.get(t.data_ptr())
-    return e is not None and e[0]() is not None and e[1] == tuple(t.shape)
+    return _relu_outputs.get(t) is not None
 
 
 class fold_skip_gradients:
@@ -1162,51 +1164,31 @@ class fold_skip_gradients:
         skip_fold = _skip_fold_allowed
         premask = _premask_allowed
         wgrad_branch = _wgrad_branch_allowed and overlap_decoders
-        _relu_outputs.clear()
-        _premasked.clear()
-        _s2d_wanted.clear()
-        _s2d_grads.clear()
-        _s2d_produced.clear()
-        _deferred.clear()
-        _unmaterialized.clear()
+        for reg in _STEP_REGISTRIES:
+            reg.clear()
         return self
 
     def __exit__(self, *exc):
         global skip_fold, premask, wgrad_branch
         skip_fold, premask, wgrad_branch = self._prev
         join_wgrad_branch()
-        _relu_outputs.clear()
-        _premasked.clear()
-        _s2d_wanted.clear()
-        _s2d_grads.clear()
-        _s2d_produced.clear()
-        _deferred.clear()
-        _unmaterialized.clear()
+        for reg in _STEP_REGISTRIES:
+            reg.clear()
         _blob_targets.clear()      # (holds the positions and the template of every Gaussian target of the step: nothing of a finished step stays alive)
         # gradients handed over to a pool whose backward never ran (an exception, a pruned graph) must not linger
-        for k in [k for k, e in _skip_registry.items() if e.consumed or e.ref() is None or e.stash]:
-            del _skip_registry[k]
+        _skip_registry.sweep(also=lambda r: r.consumed or r.stash)
         return False
 
 
 def _skip_register(x: torch.Tensor):
     # entries of finished steps (tensor gone, or the pool's backward ran) go, together with any gradient handed over
     # to a pool whose backward never ran (pruned graphs)
-    for k in [k for k, e in _skip_registry.items() if e.ref() is None or e.consumed]:
-        del _skip_registry[k]
-    e = _SkipEntry()
-    e.ref, e.shape, e.stash, e.consumed = weakref.ref(x), tuple(x.shape), [], False
-    _skip_registry[x.data_ptr()] = e
+    _skip_registry.sweep(also=lambda r: r.consumed)
+    _skip_registry.put(x, stash=[], consumed=False)
 
 
 def _skip_entry(t: torch.Tensor):
-    e = _skip_registry.get(t.data_ptr())
-    if e is None:
-        return None
-    if e.ref() is None or e.shape != tuple(t.shape):
-        del _skip_registry[t.data_ptr()]
-        return None
-    return e
+    return _skip_registry.get(t)
 
 
 class _Conv2dFn(torch.autograd.Function):
@@ -1277,8 +1259,7 @@ class _Conv2dFn(torch.autograd.Function):
         if defer:
             def run(descs=descs, wp=wp, b=b, y=y, dims=(B, H, W), cache=cache):
                 conv2d_raw(descs, None, wp, b, [(y.data_ptr(), 32, 32 * dims[1] * dims[2])], dims[0], dims[1], dims[2], 3, True, wino=(cache, "fwd"))
-            _deferred[y.data_ptr()] = {"ref": weakref.ref(y), "shape": tuple(y.shape), "run": run, "src": descs[0], "wp": wp, "bias": b, "cache": cache,
-                                       "dims": (B, H, W), "keep": keep[0]}
+            _deferred.put(y, run=run, src=descs[0], wp=wp, bias=b, cache=cache, dims=(B, H, W), keep=keep[0])
             took = None
         else:
             took = conv2d_raw(descs, None, wp, b, [(y.data_ptr(), cout, cout * H * W)], B, H, W, k, relu,
@@ -1290,9 +1271,8 @@ class _Conv2dFn(torch.autograd.Function):
         if not (isinstance(took, str) and took.endswith("|code")):
             pcode = None
         if pooled is not None:
-            for k_ in [k_ for k_, e_ in _pooled_outputs.items() if e_[0]() is None]:      # (a pool that never followed)
-                del _pooled_outputs[k_]
-            _pooled_outputs[y.data_ptr()] = (weakref.ref(y), tuple(y.shape), pooled, pcode)
+            _pooled_outputs.sweep()      # (a pool that never followed)
+            _pooled_outputs.put(y, pooled=pooled, code=pcode)
         ctx.meta = meta
         ctx.n_src = len(srcs)
         ctx.has_bias = bias is not None
@@ -1300,7 +1280,7 @@ class _Conv2dFn(torch.autograd.Function):
         ctx.save_for_backward(weight, lora_a, lora_b, y if relu else None, *keep)
         ctx.w_key = _weight_key(weight, lora_a, lora_b)
         if relu and premask:
-            _relu_outputs[y.data_ptr()] = (weakref.ref(y), tuple(y.shape), bits, k, wbits)
+            _relu_outputs.put(y, bits=bits, k=k, wbits=wbits)
         return y
 
     @staticmethod
@@ -1314,10 +1294,11 @@ class _Conv2dFn(torch.autograd.Function):
         mask = (y.data_ptr(), cout * H * W) if relu else None
         if relu and _premasked:
             # the producer of dy already zeroed it where y <= 0 (see `_premasked`): unmasked dgrad / wgrad kernels
-            if _premasked.pop(dy.data_ptr(), None) == (y.data_ptr(), dy._version, tuple(dy.shape)):
+            r = _premasked.pop(dy)
+            if r is not None and r.y_ptr == y.data_ptr():
                 mask = None
                 premask_stats["unmasked_backwards"] += 1
-        if relu and mask is not None and _unmaterialized.get(y.data_ptr()) == tuple(y.shape):
+        if relu and mask is not None and _unmaterialized.get(y) is not None:
             raise RuntimeError("conv2d backward: this convolution ran inside the fused predictor + criterion launch (its output was never written), but the gradient that "
                                "arrived does not carry its ReLU backward -- the output has another consumer, or a hook replaced its gradient: set YNET_CONV_PRED_BCE=0")
         need = ctx.needs_input_grad
@@ -1348,8 +1329,7 @@ class _Conv2dFn(torch.autograd.Function):
                     # backward sums it over the batch, as in the reference's semantic_img.expand(...))
                     d_srcs[i] = torch.empty((B, c, H, W), device=dy.device, dtype=torch.float32)
                     dsts.append((d_srcs[i].data_ptr(), c, c * H * W))
-                    w_ = _s2d_wanted.get(s.data_ptr()) if (premask and _upconv_s2d_allowed) else None
-                    want_s2d.append(bool(w_ is not None and w_[0]() is not None and w_[1] == tuple(s.shape) and c == 16 and H % 2 == 0 and W % 2 == 0))
+                    want_s2d.append(bool(premask and _upconv_s2d_allowed and _s2d_wanted.get(s) is not None and c == 16 and H % 2 == 0 and W % 2 == 0))
                 else:
                     dsts.append((None, c, 0))
                     want_s2d.append(False)
@@ -1364,20 +1344,20 @@ class _Conv2dFn(torch.autograd.Function):
                 emask = (s0.data_ptr(), s0.shape[1] * H * W)
             ebits = None
             if emask is not None:
-                e0 = _relu_outputs.get(s0.data_ptr())
-                if (e0 is not None and e0[2] is not None and e0[3] == k and d_srcs[0].data_ptr() % 16 == 0
-                        and _lib().ynet_conv2d_relu_bits_words(B, H, W, int(s0.shape[1]), int(k)) == e0[2].numel()):
-                    ebits = e0[2]          # (written by s0's own forward launch, for exactly this tiling)
+                e0 = _relu_outputs.get(s0)
+                if (e0 is not None and e0.bits is not None and e0.k == k and d_srcs[0].data_ptr() % 16 == 0
+                        and _lib().ynet_conv2d_relu_bits_words(B, H, W, int(s0.shape[1]), int(k)) == e0.bits.numel()):
+                    ebits = e0.bits        # (written by s0's own forward launch, for exactly this tiling)
             # (where the Winograd generation serves the launch it applies the float mask itself -- faster than the implicit GEMM with
             #  the 1-bit mask, whose layout belongs to that kernel's tiles)
             wino_em = (emask is not None and mask is None and bool(meta.get("wino")) and _wino_allowed and k == 3 and dy.data_ptr() % 16 == 0
                        and d_srcs[0].data_ptr() % 8 == 0 and s0.data_ptr() % 8 == 0 and dgrad_relu_family(B, H, W, cout, int(s0.shape[1]), int(k)) != 0)
             ewbits = None
             if wino_em and _wino_relu_bits_allowed and int(s0.shape[1]) == 32:
-                e0 = _relu_outputs.get(s0.data_ptr())
-                if (e0 is not None and len(e0) > 4 and e0[4] is not None and e0[4].numel() == _lib().ynet_winograd_relu_bits_words(B, H, W)
+                e0 = _relu_outputs.get(s0)
+                if (e0 is not None and e0.wbits is not None and e0.wbits.numel() == _lib().ynet_winograd_relu_bits_words(B, H, W)
                         and _lib().ynet_conv2d_winograd_supported(B, H, W, cout, 32, int(k))):
-                    ewbits = e0[4]         # (written by s0's own Winograd forward launch: the 1-bit mask in this launch's tiling)
+                    ewbits = e0.wbits      # (written by s0's own Winograd forward launch: the 1-bit mask in this launch's tiling)
             if ebits is not None and not wino_em:
                 premask_stats["bit_masks"] = premask_stats.get("bit_masks", 0) + 1
                 conv2d_raw([(dy.data_ptr(), cout, cout * H * W)], mask, wp_d, None, dsts, B, H, W, k, False, relu_bits=ebits.data_ptr())
@@ -1389,13 +1369,13 @@ class _Conv2dFn(torch.autograd.Function):
                 if s2d_info:
                     for i, g_ in enumerate(d_srcs):      # (written space-to-depth: only the up-convolution's backward may read these tensors)
                         if g_ is not None and (s2d_info.get("wrote_s2d", 0) >> i) & 1:
-                            _s2d_grads[g_.data_ptr()] = (g_._version, tuple(g_.shape))
+                            _s2d_grads.put(g_)
                             # (one hand-over per up-convolution output: a second consumer of that tensor gets a row-major gradient, and the sum autograd
                             #  forms of the two is then refused by _UpConvFn.backward instead of being read in the wrong layout)
-                            _s2d_wanted.pop(srcs[i].data_ptr(), None)
+                            _s2d_wanted.pop(srcs[i])
                             _s2d_produced.add(srcs[i].data_ptr())
             if emask is not None:
-                _premasked[d_srcs[0].data_ptr()] = (s0.data_ptr(), d_srcs[0]._version, tuple(d_srcs[0].shape))
+                _premasked.put(d_srcs[0], y_ptr=s0.data_ptr())
             if skip_fold:
                 for i, s in enumerate(srcs):
                     if d_srcs[i] is None:
@@ -1630,13 +1610,10 @@ def release_stale_entries():
     """Drop the per-step registry entries whose tensors are gone.  A forward / backward outside fold_skip_gradients() (forward_test,
     YNetTrainer.saliency) registers pooled copies and Gaussian targets that only the next registration would sweep; the entries
     hold device tensors (the pooled maps, the target positions).  Not for use inside a step."""
-    for reg in (_pooled_outputs, _blob_targets, _relu_outputs, _s2d_wanted):
-        for k in [k for k, e in reg.items() if e[0]() is None]:
-            del reg[k]
-    for k in [k for k, e in _deferred.items() if e["ref"]() is None]:
-        del _deferred[k]
-    for k in [k for k, e in _skip_registry.items() if e.ref() is None or e.consumed]:
-        del _skip_registry[k]
+    for reg in _ALL_REGISTRIES:
+        if reg.weak:
+            reg.sweep()
+    _skip_registry.sweep(also=lambda r: r.consumed)
 
 
 def add_range_noise(x: torch.Tensor, frac: float, seed: int) -> torch.Tensor:
@@ -1678,8 +1655,8 @@ class _PyramidFn(torch.autograd.Function):
 # pooling / resampling
 # ------------------------------------------------------------------------------------------------
 # conv outputs whose 2 x 2 max-pooled copy was written by the conv's own epilogue (ops.conv2d(..., pool=True)):
-# address of y -> (weak reference to y, its shape, the pooled tensor); consumed by the max_pool2 call that follows
-_pooled_outputs = {}
+# y -> pooled (the pooled tensor), code (the pool's backward byte per block, or None); consumed by the max_pool2 call that follows
+_pooled_outputs = Handover("pooled_outputs", step=False)
 pool_code_stats = {"launches": 0}
 _pool_epilogue_allowed = _os.environ.get("YNET_POOL_EPILOGUE", "1") != "0"
 
@@ -1690,11 +1667,11 @@ class _MaxPool2Fn(torch.autograd.Function):
         _need_gpu(x, "max_pool2d")
         x = x.contiguous()
         B, C, H, W = x.shape
-        e = _pooled_outputs.pop(x.data_ptr(), None) if _pooled_outputs else None
+        e = _pooled_outputs.pop(x) if _pooled_outputs else None
         ctx.code = None
-        if e is not None and e[0]() is x and e[1] == tuple(x.shape) and x._version == 0:
-            y = e[2]                 # written by the producing conv's epilogue: no pass over x here
-            ctx.code = e[3] if len(e) > 3 else None      # (... and, from a Winograd launch, arg-max + ReLU bits per block for backward)
+        if e is not None and e.ref() is x and x._version == 0:
+            y = e.pooled             # written by the producing conv's epilogue: no pass over x here
+            ctx.code = e.code        # (... and, from a Winograd launch, arg-max + ReLU bits per block for backward)
         else:
             y = torch.empty((B, C, H // 2, W // 2), device=x.device, dtype=torch.float32)
             lib = _lib()
@@ -1738,7 +1715,7 @@ class _MaxPool2Fn(torch.autograd.Function):
                                                   a1.data_ptr() if a1 is not None else None, dx.data_ptr(), B * C, H, W,
                                                   1 if pm else 0, _stream()), lib)
             if pm:
-                _premasked[dx.data_ptr()] = (x.data_ptr(), dx._version, tuple(dx.shape))
+                _premasked.put(dx, y_ptr=x.data_ptr())
         else:
             L.check(lib.ynet_maxpool2_bwd(x.data_ptr(), dy.contiguous().data_ptr(), dx.data_ptr(), B * C, H, W, _stream()), lib)
         return dx
@@ -1771,7 +1748,7 @@ class _Upsample2xFn(torch.autograd.Function):
         lib = _lib()
         if ctx.premask and premask and x is not None:
             L.check(lib.ynet_upsample2x_bwd_relu(dy.contiguous().data_ptr(), dx.data_ptr(), x.data_ptr(), B * C, H, W, _stream()), lib)
-            _premasked[dx.data_ptr()] = (x.data_ptr(), dx._version, tuple(dx.shape))
+            _premasked.put(dx, y_ptr=x.data_ptr())
         else:
             L.check(lib.ynet_upsample2x_bwd(dy.contiguous().data_ptr(), dx.data_ptr(), B * C, H, W, _stream()), lib)
         return dx
@@ -1799,8 +1776,8 @@ def upsample2x_conv2d_raw(src, u, bias, dst, cin, cout, B, H, W, relu=False):
 # space-to-depth (one plain 16-channel Winograd launch: the decoders' last level) and registers the gradient; _UpConvFn.backward, handed a registered gradient, runs the
 # effective-filter data gradient at the low resolution + the ring correction instead of [data gradient at the up-sampled size -> bilinear backward].
 _upconv_s2d_allowed = _os.environ.get("YNET_UPCONV_S2D", "1") != "0"
-_s2d_wanted = {}       # output of an up-convolution: data_ptr -> (weakref, shape)
-_s2d_grads = {}        # a gradient written space-to-depth: data_ptr -> (version, shape)
+_s2d_wanted = Handover("s2d_wanted")                                 # output of an up-convolution whose gradient may arrive space-to-depth
+_s2d_grads = Handover("s2d_grads", weak=False, version=True)         # a gradient written space-to-depth
 # ---- the last decoder convolution inside the fused predictor + criterion (round 6; ynet_conv2d_winograd_pred_bce_blob) -------------------------------------------
 # `conv2d(..., defer=True)` (a frozen 32 -> 32 conv + ReLU under fold_skip_gradients()) builds its autograd node but launches nothing: its output tensor is registered
 # here, and the pred_bce call that consumes it runs [convolution -> predictor -> criterion -> predictor's data gradient] as ONE launch -- the 32 activation planes are
@@ -1808,8 +1785,8 @@ _s2d_grads = {}        # a gradient written space-to-depth: data_ptr -> (version
 # backward receives the fused launch's dx, which carries that convolution's ReLU backward already (`_premasked`); a backward that would need the activation itself
 # (its mask was not applied by the producer) is refused loudly.
 _conv_pred_bce_allowed = _os.environ.get("YNET_CONV_PRED_BCE", "1") != "0"
-_deferred = {}         # data_ptr of y -> dict(ref, shape, run) : convolutions not yet launched
-_unmaterialized = {}   # data_ptr of y -> shape : outputs whose convolution ran inside the fused launch (the memory holds nothing)
+_deferred = Handover("deferred")                                     # y -> run, src, wp, bias, cache, dims, keep : convolutions not yet launched
+_unmaterialized = Handover("unmaterialized", weak=False)             # y : outputs whose convolution ran inside the fused launch (the memory holds nothing)
 conv_pred_bce_stats = {"fused": 0, "materialized": 0}
 
 
@@ -1817,15 +1794,15 @@ def materialize_deferred(t):
     """Launch the convolution behind `t` if it was deferred (see above); a no-op for every other tensor."""
     if not _deferred or not torch.is_tensor(t):
         return t
-    e = _deferred.get(t.data_ptr())
-    if e is not None and e["ref"]() is not None and e["shape"] == tuple(t.shape):
-        del _deferred[t.data_ptr()]
-        e["run"]()
+    e = _deferred.pop(t)
+    if e is not None:
+        e.run()
         conv_pred_bce_stats["materialized"] += 1
     return t
 
 
 _s2d_produced = set()  # outputs of up-convolutions (data_ptr) for which a gradient WAS written space-to-depth: their backward must be handed exactly that tensor
+_STEP_REGISTRIES.append(_s2d_produced)      # (a plain set, emptied with the step's registries: _UpConvFn.backward has the address alone, the output may be gone by then)
 upconv_stats_s2d = {"backwards": 0}
 _S2D_M = ((0.75, 0.25, 0.0), (0.25, 0.75, 0.75), (0.0, 0.0, 0.25)), ((0.25, 0.0, 0.0), (0.75, 0.75, 0.25), (0.0, 0.25, 0.75))
 _S2D_DM = ((-0.25, 0.25, 0.0), (0.25, 0.0, 0.0)), ((0.0, 0.0, 0.25), (0.0, 0.25, -0.25))
@@ -1949,7 +1926,7 @@ class _UpConvFn(torch.autograd.Function):
         if (_upconv_s2d_allowed and premask and ctx.needs_input_grad[0] and cout == 16 and x.data_ptr() % 16 == 0
                 and _wino16_supported([4 * cout], cin, B, Hl, Wl)):
             # (inside fold_skip_gradients(): the gradient of y may arrive space-to-depth -- see the protocol above)
-            _s2d_wanted[y.data_ptr()] = (weakref.ref(y), tuple(y.shape))
+            _s2d_wanted.put(y)
         ctx.y_ptr = y.data_ptr()
         return y
 
@@ -1961,8 +1938,7 @@ class _UpConvFn(torch.autograd.Function):
         if ctx.w_key != _weight_key(weight, None, None):
             raise RuntimeError("upsample2x_conv2d backward: the filter was modified in place between forward and backward")
         dy = dy.contiguous()
-        reg = _s2d_grads.pop(dy.data_ptr(), None)
-        handed = reg is not None and reg == (dy._version, tuple(dy.shape))
+        handed = _s2d_grads.pop(dy) is not None
         if ctx.y_ptr in _s2d_produced:
             _s2d_produced.discard(ctx.y_ptr)
             if not handed:
@@ -1986,7 +1962,7 @@ class _UpConvFn(torch.autograd.Function):
                 L.check(lib.ynet_upconv_dgrad_ring(dy.data_ptr(), 4 * cout * Hl * Wl, tables.data_ptr(), x.data_ptr() if masked else None, cin * Hl * Wl, dx.data_ptr(),
                                                    cin * Hl * Wl, B, 4 * cout, cin, Hl, Wl, _stream()), lib)
             if masked:
-                _premasked[dx.data_ptr()] = (x.data_ptr(), dx._version, tuple(dx.shape))
+                _premasked.put(dx, y_ptr=x.data_ptr())
             upconv_stats_s2d["backwards"] += 1
             return dx, None, None, None
         wp_d = _cached(ctx.cache, weight, None, None, 1.0, "dgrad")
@@ -1996,7 +1972,7 @@ class _UpConvFn(torch.autograd.Function):
         lib = _lib()
         if ctx.premask and premask and x is not None:
             L.check(lib.ynet_upsample2x_bwd_relu(d_up.data_ptr(), dx.data_ptr(), x.data_ptr(), B * cin, Hl, Wl, _stream()), lib)
-            _premasked[dx.data_ptr()] = (x.data_ptr(), dx._version, tuple(dx.shape))
+            _premasked.put(dx, y_ptr=x.data_ptr())
         else:
             L.check(lib.ynet_upsample2x_bwd(d_up.data_ptr(), dx.data_ptr(), B * cin, Hl, Wl, _stream()), lib)
         return dx, None, None, None
@@ -2155,6 +2131,18 @@ class _BCEFn(torch.autograd.Function):
 _pred_bce_ws = {}
 
 
+def _pred_bce_setup(lib, device, expected_grad):
+    """(the current stream's workspace, zero-filled when it is made; `expected_grad` as a finite non-zero float, 1.0 in place of anything else)"""
+    key = (device, torch.cuda.current_stream().cuda_stream)
+    ws = _pred_bce_ws.get(key)
+    if ws is None:
+        ws = _pred_bce_ws[key] = torch.zeros(lib.ynet_pred_bce_workspace_bytes() // 8 + 1, device=device, dtype=torch.float64)
+    expected_grad = float(expected_grad)
+    if not (expected_grad != 0.0 and abs(expected_grad) < float("inf")):
+        expected_grad = 1.0
+    return ws, expected_grad
+
+
 class _PredBCEFn(torch.autograd.Function):
     """(logits, loss) = (conv1x1(x, W) + b, mean BCE(logits, target)).  The forward kernel also leaves the gradients
     for the upstream gradient `expected_grad` of the loss: dx for the decoder (the predictor's dgrad) and, when the
@@ -2164,8 +2152,8 @@ class _PredBCEFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, target, expected_grad, cache):
         _need_gpu(x, "pred_bce input")
         _need_gpu(target, "pred_bce target")
-        dfr = _deferred.get(x.data_ptr()) if _deferred else None      # x = the output of a convolution that has not been launched yet (see `_deferred`)
-        if dfr is not None and not (dfr["ref"]() is not None and dfr["shape"] == tuple(x.shape) and x.is_contiguous()):
+        dfr = _deferred.get(x) if _deferred else None      # x = the output of a convolution that has not been launched yet (see `_deferred`)
+        if dfr is not None and not x.is_contiguous():
             dfr = None
         x, target = x.contiguous(), target.contiguous()
         B, cin, H, W = x.shape
@@ -2177,31 +2165,25 @@ class _PredBCEFn(torch.autograd.Function):
         if dfr is not None:
             need_w_ = ctx.needs_input_grad[1] or (bias is not None and ctx.needs_input_grad[2])
             blob_t_ = _blob_target(target, B, cout, H, W)
-            if (ctx.needs_input_grad[0] and not need_w_ and blob_t_ is not None and premask and cin == 32 and dfr["dims"] == (B, H, W)
+            if (ctx.needs_input_grad[0] and not need_w_ and blob_t_ is not None and premask and cin == 32 and dfr.dims == (B, H, W)
                     and lib.ynet_conv2d_winograd_pred_bce_supported(B, H, W, 32, 32, cout, int(blob_t_[1].blob.shape[0]))):
                 # ONE launch: the convolution, its ReLU, the predictor, the criterion and the predictor's data gradient (through that ReLU's backward)
-                del _deferred[x.data_ptr()]
+                _deferred.pop(x)
                 pos, tmpl = blob_t_
                 pos.record_stream(torch.cuda.current_stream(x.device))
                 y = torch.empty((B, cout, H, W), device=x.device, dtype=torch.float32)
                 loss = torch.empty((), device=x.device, dtype=torch.float32)
-                key = (x.device, torch.cuda.current_stream().cuda_stream)
-                ws = _pred_bce_ws.get(key)
-                if ws is None:
-                    ws = _pred_bce_ws[key] = torch.zeros(lib.ynet_pred_bce_workspace_bytes() // 8 + 1, device=x.device, dtype=torch.float64)
-                expected_grad = float(expected_grad)
-                if not (expected_grad != 0.0 and abs(expected_grad) < float("inf")):
-                    expected_grad = 1.0
-                u = _wino_filter((dfr["cache"], "fwd"), "wino", dfr["wp"], 0, (32,), 32, 0, 32).u      # (the entry _conv2d_raw_py keeps for the unfused launch of the same layer)
+                ws, expected_grad = _pred_bce_setup(lib, x.device, expected_grad)
+                u = _wino_filter((dfr.cache, "fwd"), "wino", dfr.wp, 0, (32,), 32, 0, 32).u      # (the entry _conv2d_raw_py keeps for the unfused launch of the same layer)
                 ctx.dx = torch.empty_like(x)
                 ctx.dy = None
-                conv2d_winograd_pred_bce_raw(dfr["src"], u, dfr["bias"], wp, bias.detach() if bias is not None else None, cout, pos, tmpl, y, loss, ctx.dx, ws,
+                conv2d_winograd_pred_bce_raw(dfr.src, u, dfr.bias, wp, bias.detach() if bias is not None else None, cout, pos, tmpl, y, loss, ctx.dx, ws,
                                              B, H, W, expected_grad)
                 bce_blob_stats["launches"] += 1
                 conv_pred_bce_stats["fused"] += 1
-                _unmaterialized[x.data_ptr()] = tuple(x.shape)
+                _unmaterialized.put(x)
                 ctx.premask_y = x.data_ptr()
-                ctx.blob_keep = (pos, tmpl, dfr["keep"])
+                ctx.blob_keep = (pos, tmpl, dfr.keep)
                 ctx.expected = expected_grad
                 ctx.has_bias = bias is not None
                 ctx.save_for_backward(x, weight)
@@ -2211,13 +2193,7 @@ class _PredBCEFn(torch.autograd.Function):
             materialize_deferred(x)
         y = torch.empty((B, cout, H, W), device=x.device, dtype=torch.float32)
         loss = torch.empty((), device=x.device, dtype=torch.float32)
-        key = (x.device, torch.cuda.current_stream().cuda_stream)
-        ws = _pred_bce_ws.get(key)
-        if ws is None:
-            ws = _pred_bce_ws[key] = torch.zeros(lib.ynet_pred_bce_workspace_bytes() // 8 + 1, device=x.device, dtype=torch.float64)
-        expected_grad = float(expected_grad)
-        if not (expected_grad != 0.0 and abs(expected_grad) < float("inf")):
-            expected_grad = 1.0
+        ws, expected_grad = _pred_bce_setup(lib, x.device, expected_grad)
         need_x = ctx.needs_input_grad[0]
         need_w = ctx.needs_input_grad[1] or (bias is not None and ctx.needs_input_grad[2])
         ctx.dx = torch.empty_like(x) if need_x else None
@@ -2263,7 +2239,7 @@ class _PredBCEFn(torch.autograd.Function):
         if dx is not None:
             L.check(lib.ynet_bce_grad_rescale(dx.data_ptr(), g.data_ptr(), ctx.expected, dx.numel(), _stream()), lib)
             if ctx.premask_y is not None and premask:
-                _premasked[dx.data_ptr()] = (ctx.premask_y, dx._version, tuple(dx.shape))
+                _premasked.put(dx, y_ptr=ctx.premask_y)
         if dy is not None:
             L.check(lib.ynet_bce_grad_rescale(dy.data_ptr(), g.data_ptr(), ctx.expected, dy.numel(), _stream()), lib)
             d_w, d_b = conv2d_wgrad_raw([x], dy, None, weight, ctx.has_bias and ctx.needs_input_grad[2])
@@ -2507,27 +2483,27 @@ def _analytic_patches(t: AnalyticTemplate, xy, H: int, W: int) -> torch.Tensor:
     if t.kind == "gaussian" and _bce_blob_allowed:
         # the fused predictor + criterion computes such a target from the positions instead of reading its planes (ynet_pred_bce_blob):
         # remembered by storage, size and version -- a tensor somebody wrote into since is read as the tensor it is
-        for k_ in [k_ for k_, e_ in _blob_targets.items() if e_[0]() is None]:
-            del _blob_targets[k_]
-        _blob_targets[out.data_ptr()] = (weakref.ref(out), out._version, n, H, W, coords, t, coords._version)
+        _blob_targets.sweep()
+        _blob_targets.put(out, n=n, H=H, W=W, coords=coords, tmpl=t, coords_version=coords._version)
     return out
 
 
 _bce_blob_allowed = _os.environ.get("YNET_BCE_BLOB_TARGET", "1") != "0"      # (development switch)
-_blob_targets = {}
+# target `out` [n, H, W] -> n, H, W, coords, tmpl, coords_version.  (No shape check: the target is consumed as a [B, cout, H, W] view of the tensor registered.
+# step=False: fold_skip_gradients() leaves it alone on enter and empties it by name on exit.)
+_blob_targets = Handover("blob_targets", shape=False, version=True, step=False)
 bce_blob_stats = {"launches": 0}
 
 
 def _blob_target(target, B, cout, H, W):
     """(positions [B * cout, 2], AnalyticTemplate) if `target` [B, cout, H, W] is, untouched, what gather_patches wrote for a Gaussian template."""
-    e = _blob_targets.get(target.data_ptr()) if _bce_blob_allowed else None
-    if (e is None or e[0]() is None or not target.is_contiguous() or target._version != e[1] or (e[2], e[3], e[4]) != (B * cout, H, W) or W % 4 != 0
-            or e[5]._version != e[7]):
+    e = _blob_targets.get(target) if _bce_blob_allowed else None
+    if e is None or not target.is_contiguous() or (e.n, e.H, e.W) != (B * cout, H, W) or W % 4 != 0 or e.coords._version != e.coords_version:
         return None
-    base = e[0]()
+    base = e.ref()
     if base.untyped_storage().data_ptr() != target.untyped_storage().data_ptr() or target.numel() != base.numel():
         return None
-    return e[5], e[6]
+    return e.coords, e.tmpl
 
 
 def pad_planes(x: torch.Tensor, division_factor: int = 32) -> torch.Tensor:

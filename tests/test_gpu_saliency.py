@@ -270,9 +270,9 @@ def test_saliency_leaves_the_training_step_unchanged(dev):
     c1 = counters()
     t = _trainer(cfg, sd, dev, traj.shape[0])
     t.saliency(_df(traj, cfg), {"scene0": scene[0]})
-    for reg in (ops._relu_outputs, ops._premasked, ops._skip_registry, ops._deferred, ops._unmaterialized, ops._s2d_wanted):
+    for reg in (*ops._STEP_REGISTRIES, ops._skip_registry):
         assert not reg, reg
-    assert not any(e[0]() is not None for e in ops._pooled_outputs.values()) and not ops._blob_targets
+    assert not any(e.ref() is not None for e in ops._pooled_outputs.values()) and not ops._blob_targets
     c2 = counters()
     loss_b, grads_b = _step(cfg, sd, dev, scene, traj)
     c3 = counters()
