@@ -534,6 +534,35 @@ int ynet_sigmoid_temp(const float* x, float* y, long long B, int C, long long HW
 int ynet_map_likelihood(const float* x, long long batch_stride, const float* gt_xy, long long B, int C, int H, int W, float temperature,
                         float* nll, float* entropy, float* hpd, int* status, void* stream);
 
+/* Deterministic goal modes of the goal map: greedy non-maximum suppression over the logits the goals are sampled from
+ * (pred_goal_map, utils/evaluate.py:128-131; the reference has no deterministic multi-modal read-out: its soft-argmax is the mean of
+ * the map).  Per plane (b, c) of x [B][C][H][W] (batch stride `batch_stride` elements, so a channel slice needs no copy), all
+ * comparisons on the raw fp32 logits as IEEE values (-0.0 == +0.0, denormals are not flushed, +inf is an ordinary largest value):
+ *   1. candidates: the pixels with x > -inf
+ *   2. mode m (m = 0 .. n_modes - 1): the not-yet-suppressed candidate with the largest logit; a tie goes to the smallest linear
+ *      index row * W + col
+ *   3. the mode suppresses every pixel with drow^2 + dcol^2 <= radius^2 (integers; radius 0: the pixel alone)
+ *   4. stop when no candidate is left; count [B][C] = the number of modes found
+ *   5. mass [B][C][M] = (sum of sigmoid(x_i / T) over the pixels mode m NEWLY suppressed: inside its disk, in no earlier mode's) / Z,
+ *      Z = the sum over the whole plane: the masses are disjoint and sum to the covered share (<= 1).  A -inf pixel adds 0.  The
+ *      terms are fp32 (formed as ynet_map_likelihood forms them: sigmoids below fp32's range count as 0, so Z == 0 gives NaN masses),
+ *      the sums fp64, assigned to threads and combined in a fixed order, with no floating-point atomics: two runs give the same bits.
+ *      `temperature` is read only when mass is given; mass may be NULL.
+ *   6. entries m >= count: xy = (-1, -1), logit = -inf, mass = 0
+ *   7. a plane that holds a NaN: count = -1, every entry gets those fill values, *status |= 1 (device int, zero it first); nothing is
+ *      ranked in such a plane
+ *   8. a plane of -inf only: count = 0
+ * xy [B][C][M][2] holds (x, y) = (column, row) as integer-valued fp32, what `sampling` returns (utils/image_utils.py:110-135);
+ * logit [B][C][M] the mode's raw logit.
+ * One workgroup per plane; the plane is read once, the rounds work on a table of per-segment maxima and a suppression bitmap of H * W
+ * bits in LDS.  That bitmap sets the cap: H * W <= YNET_MAP_MODES_MAX_PIXELS = 262144 (512 x 512: 32 KB of bits + 8 KB of table, inside
+ * the 64 KB a workgroup gets without opting into more of the CU's LDS).  64-bit offsets; B * C <= 4194303 planes.
+ * Refused (non-zero, ynet_last_error) before any launch: null x, xy, logit, count or status; n_modes outside 1 .. 64; radius < 0;
+ * B, C, H or W < 1; H * W above the cap; batch_stride < C * H * W; with mass: temperature <= 0, not finite, or below 2.95e-39. */
+#define YNET_MAP_MODES_MAX_PIXELS 262144
+int ynet_map_modes(const float* x, long long batch_stride, long long B, int C, int H, int W, int n_modes, int radius, float temperature,
+                   float* xy, float* logit, float* mass, int* count, int* status, void* stream);
+
 /* ---- heat-map construction -------------------------------------------------------------------- */
 /* get_patch + torch.stack (utils/image_utils.py:40-63; utils/train_epoch.py:63-78;
  * utils/evaluate.py:112-114,250-253): out[n] = tmpl[SH/2 - ry : +H, SW/2 - rx : +W] with

@@ -332,13 +332,13 @@ class YNetTrainer:
 
     def _predict(self, df_obs, image_path, dataset_name, resize_factor, obs_len, waypoints, n_goal, n_traj, temperature,
                  batch_size=None, rel_threshold=0.002, use_TTST=False, use_CWS=False, CWS_params=None, use_raw_data=False,
-                 network=None, swap_semantic=False, return_maps=False, bank=None, style_column=None, **kwargs):
+                 network=None, swap_semantic=False, return_maps=False, bank=None, style_column=None, modes=None, **kwargs):
         import pandas as pd
-        from ..utils.predict import MAX_SAMPLES, predict, predict_styles
+        from ..utils.predict import MAX_SAMPLES, predict, predict_modes, predict_styles
         if dataset_name.lower() == "eth":
             raise NotImplementedError("predict: ETH/UCY forecasts are in world coordinates (homographies read from data files): "
                                       "out of the MI355X hot path, as in prepare_data")
-        if n_goal * n_traj > MAX_SAMPLES:
+        if modes is None and n_goal * n_traj > MAX_SAMPLES:
             raise ValueError(f"predict: n_goal * n_traj = {n_goal * n_traj} samples per agent; the ranking kernel takes up to {MAX_SAMPLES}")
         if isinstance(df_obs, dict):
             rows, first = [], 0
@@ -370,7 +370,11 @@ class YNetTrainer:
         for observed, meta, scene_id in loader:
             kw = dict(use_TTST=use_TTST, use_CWS=use_CWS, rel_thresh=rel_threshold, CWS_params=CWS_params, network=network,
                       swap_semantic=swap_semantic, batch_size=batch_size, return_maps=return_maps)
-            if bank is None:
+            if modes is not None:      # (n_modes, radius): no draw, so none of the sampling options
+                res = predict_modes(model, images[scene_id], observed, input_template, waypoints, *modes, obs_len, resize_factor, temperature,
+                                    CWS_params=CWS_params if use_CWS else None, network=network, swap_semantic=swap_semantic,
+                                    batch_size=batch_size, return_maps=return_maps)
+            elif bank is None:
                 res = predict(model, images[scene_id], observed, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature, **kw)
             else:
                 styles = meta[0][style_column].to_numpy().reshape(-1, obs_len)
@@ -383,6 +387,8 @@ class YNetTrainer:
             n, k = scores.shape
             frames.append(pd.DataFrame({"metaId": np.repeat(meta[0].metaId.unique(), k), "sceneId": [scene_id] * (n * k),
                                         "rank": np.tile(np.arange(k), n), "score": scores.reshape(-1)}))
+            if modes is not None:
+                frames[-1]["mass"] = res["mode_mass"].cpu().numpy().reshape(-1)
         return results, pd.concat(frames, ignore_index=True)
 
     def load_styles(self, pretrained_path, styles):
@@ -406,6 +412,17 @@ class YNetTrainer:
         for name in df_obs[style_column].unique():
             bank.index(name)      # (an unknown style is refused before any scene runs)
         return self._predict(df_obs, image_path_or_images, return_maps=return_maps, bank=bank, style_column=style_column, **self.params)
+
+    def predict_modes(self, df_obs, image_path_or_images, n_modes, radius, return_maps=False):
+        """predict() with no draw: the ``n_modes`` most likely futures of every agent, their goals read off the goal map by greedy
+        non-maximum suppression with a disk of ``radius`` pixels (of the resized map), each with the probability mass it claims
+        (utils.predict.predict_modes).  ``df_obs`` and ``image_path_or_images`` as for predict(); n_goal, n_traj and use_TTST of the
+        parameters are not read, and with use_CWS the intermediate way-points are CWS expectations.
+        -> as predict(); every scene's dict carries ``mode_mass`` and ``mode_logit``, and the DataFrame a ``mass`` column."""
+        n_modes, radius = int(n_modes), int(radius)
+        if not 1 <= n_modes <= 64 or radius < 0:      # (before any scene is prepared; utils.predict.predict_modes says why)
+            raise ValueError(f"predict_modes: n_modes = {n_modes} (1 .. 64), radius = {radius} (>= 0)")
+        return self._predict(df_obs, image_path_or_images, return_maps=return_maps, modes=(n_modes, radius), **self.params)
 
     # ------------------------------------------------------------------------------------------
     def forward_test(self, df_test, image_path, set_input, noisy_std_frac):

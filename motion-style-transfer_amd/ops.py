@@ -2847,6 +2847,53 @@ def check_likelihood_status(raise_error: bool = True) -> bool:
     return hit
 
 
+_modes_status = {}
+MAX_MODES = 64      # ynet_map_modes takes up to the MAX_SAMPLES of the ranking kernel
+
+
+def map_modes(x: torch.Tensor, n_modes: int, radius: int, temperature: float = 1.0, want_mass: bool = True):
+    """The deterministic modes of every plane of the logits x [B, C, H, W] by greedy non-maximum suppression (ynet_map_modes; the
+    logits of utils/evaluate.py:128-131): mode m is the unsuppressed pixel with the largest logit (ties: the smallest row * W + col),
+    it suppresses the disk of ``radius`` pixels around it and claims the share of sigmoid(x / T) / Z it newly suppressed.
+    -> dict of device tensors: ``xy`` [B, C, M, 2] (x, y) = (column, row) as `sampling` returns them, ``logit`` [B, C, M], ``count``
+    [B, C] int32 (modes found; the entries from there on hold (-1, -1), -inf and 0), and with ``want_mass`` ``mass`` [B, C, M].
+    A channel view such as x[:, -1:] is read in place.  Not differentiable.  A plane that holds a NaN is not ranked: count -1, and
+    the next check_modes_status() raises."""
+    t, c, bs = _plane_desc(x.detach() if torch.is_tensor(x) else x, "map_modes")
+    B, _, H, W = t.shape
+    M, radius = int(n_modes), int(radius)
+    if not 1 <= M <= MAX_MODES:
+        raise ValueError(f"map_modes: n_modes = {M}, expected 1 .. {MAX_MODES}")
+    if radius < 0:
+        raise ValueError(f"map_modes: radius = {radius} is negative")
+    if want_mass and not (float(temperature) > 0 and np.isfinite(float(temperature))):
+        raise ValueError(f"map_modes: temperature {temperature!r} must be positive and finite")
+    dev = t.device
+    out = {"xy": torch.empty((B, c, M, 2), device=dev, dtype=torch.float32), "logit": torch.empty((B, c, M), device=dev, dtype=torch.float32),
+           "count": torch.empty((B, c), device=dev, dtype=torch.int32)}
+    if want_mass:
+        out["mass"] = torch.empty((B, c, M), device=dev, dtype=torch.float32)
+    st = _status_flag(_modes_status, dev)
+    lib = _lib()
+    L.check(lib.ynet_map_modes(t.data_ptr(), bs, B, c, H, W, M, radius, float(temperature) if want_mass else 1.0, out["xy"].data_ptr(),
+                               out["logit"].data_ptr(), out["mass"].data_ptr() if want_mass else None, out["count"].data_ptr(),
+                               st.data_ptr(), _stream()), lib)
+    return out
+
+
+def check_modes_status(raise_error: bool = True) -> bool:
+    """Raise if a map_modes call met a plane that holds a NaN (checked at a sync point); the flag is cleared.
+    raise_error=False: report it instead (-> True if one did) -- predict_modes names the agent itself."""
+    hit = False
+    for dev, st in _modes_status.items():
+        if int(st.item()) != 0:
+            st.zero_()
+            hit = True
+    if hit and raise_error:
+        raise RuntimeError("map_modes: a plane holds a NaN logit (it was not ranked: its count is -1)")
+    return hit
+
+
 def check_patch_status():
     """Raise if a device-side coordinate ever left the template (checked at sync points)."""
     for dev, st in _patch_status.items():

@@ -12,9 +12,13 @@ that batch.  Nothing is captured into a hipGraph here; evaluate()'s captured-swe
 
 ``predict_styles`` is predict() for a scene whose agents wear different styles: one frozen model, the adapter sets of a
 models.style_bank.StyleBank, one call.
+
+``predict_modes`` is predict() with no draw at all: the goals are the modes of the goal map's logits under greedy non-maximum
+suppression (ops.map_modes), each with the probability mass it claims.
 """
 import functools
 import inspect
+import math
 
 import numpy as np
 import torch
@@ -68,10 +72,47 @@ def _validated(name, observed, scene_image, waypoints, n_goal, n_traj, obs_len, 
     return obs.float(), waypoints, n_goal, n_traj, obs_len, style_index
 
 
+def disk_area(radius):
+    """A(r) = #{(dx, dy) : dx^2 + dy^2 <= r^2}: the pixels one mode suppresses at most"""
+    r = int(radius)
+    return sum(2 * math.isqrt(r * r - dx * dx) + 1 for dx in range(-r, r + 1))
+
+
+def _check_modes_fit(name, n_modes, radius, H, W):
+    """(n_modes - 1) * A(radius) < H * W: the first n_modes - 1 disks cannot cover the map, so finite logits always give n_modes modes"""
+    area = disk_area(min(radius, H + W))      # (beyond H + W a disk holds the whole map anyway)
+    if (n_modes - 1) * area >= H * W:
+        raise ValueError(f"{name}: {n_modes} modes of radius {radius} ({area} pixels each) may not fit the {H}x{W} map: "
+                         f"(n_modes - 1) * A(radius) = {(n_modes - 1) * area} >= {H * W}; ask for fewer modes or a smaller radius")
+
+
+def _mode_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, n_modes, radius, obs_len, temperature, device, CWS_params):
+    """The way-points of predict_modes for one chunk, with no draw -> ([n_modes, n, n_wp, 2], {"mass", "logit": [n, n_modes] in mode
+    order, "short": [n] bool, an agent with fewer modes than asked for}).
+    Goals: the modes of the RAW goal logits (a saturated fp32 sigmoid ties pixels whose logits differ).  Intermediate way-points: with
+    CWS_params the expectation chain of cws_waypoints (n_traj = 1: no `sampling` call); without, the top pixel of each intermediate
+    plane's logits, shared by the modes.  An entry no mode filled is (-1, -1): it is moved onto pixel (0, 0), so that the chunk's
+    launches stay inside the map until its sync point, where _forecast raises."""
+    last = waypoints[-1]
+    goal = ops.map_modes(pred_goal_map[:, last:last + 1], n_modes, radius, temperature)
+    found = {"mass": goal["mass"][:, 0], "logit": goal["logit"][:, 0], "short": goal["count"][:, 0] < n_modes}
+    goals = goal["xy"][:, 0].clamp_min(0.0).permute(1, 0, 2).unsqueeze(2)      # [n_modes, n, 1, 2]
+    if len(waypoints) == 1 or CWS_params is not None:
+        return _draw_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, n_modes, 1, obs_len, device, use_CWS=CWS_params is not None,
+                               CWS_params=CWS_params, forced_goals=goals), found
+    tops = [ops.map_modes(pred_goal_map[:, w:w + 1], 1, 0, want_mass=False) for w in waypoints[:-1]]
+    for t in tops:
+        found["short"] = found["short"] | (t["count"][:, 0] < 1)
+    inter = torch.stack([t["xy"][:, 0, 0] for t in tops], dim=1).clamp_min(0.0)      # [n, n_wp - 1, 2]
+    return torch.cat([inter.unsqueeze(0).expand(n_modes, -1, -1, -1), goals], dim=2), found
+
+
 def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
               use_TTST, use_CWS, rel_thresh, CWS_params, network, swap_semantic, batch_size, max_effective_batch, forced_samples, return_maps,
-              return_entropy):
-    """The one body of predict(), predict_with_entropy() and predict_styles(), on arguments that went through _validated.
+              return_entropy, modes=None):
+    """The one body of predict(), predict_with_entropy(), predict_styles() and predict_modes(), on arguments that went through _validated.
+    modes              None, or (n_modes, radius): the way-points are not drawn but read off the goal map (_mode_waypoints; then
+                       n_goal = n_modes, n_traj = 1, and the results gain ``mode_mass`` and ``mode_logit``)
     refresh()          packs the filters the chunks will read, on the caller's stream, before the decoder passes fan out over two (see
                        evaluate()): ops.refresh_filters(model), or a StyleBank's refresh() for its shadows and the shared layers
     chunk_plan(b, n)   for the n agents from b on -> (perm, pred_features): ``perm`` None, or the order the chunk runs in (row j of the
@@ -86,7 +127,7 @@ def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template
     was_training = model.training
     model.eval()
     out = {k: [] for k in ["trajectories", "waypoints", "scores", "order"] + (["goal_map", "goal_sigmoid_map"] if return_maps else [])
-           + (["entropy"] if return_entropy else [])}
+           + (["entropy"] if return_entropy else []) + (["mode_mass", "mode_logit"] if modes is not None else [])}
     try:
         with torch.no_grad():
             refresh()
@@ -97,6 +138,8 @@ def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template
             if network == "embed":
                 scene = model.scene_embedding(scene)
             _, _, H, W = scene.shape
+            if modes is not None:
+                _check_modes_fit(name, *modes, H, W)
             for b in range(0, N, step):
                 batch = obs[b:b + step]
                 n = len(batch)
@@ -116,6 +159,9 @@ def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template
                     if mixed:      # a row gather inside each of the K slabs
                         slab_rows = (torch.arange(K, device=device, dtype=torch.int32)[:, None] * n + perm_dev[None]).reshape(-1)
                         waypoint_samples = ops.gather_rows(waypoint_samples.float().contiguous().view(K * n, n_wp, 2), slab_rows).view(K, n, n_wp, 2)
+                elif modes is not None:
+                    waypoint_samples, found = _mode_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, *modes, obs_len, temperature,
+                                                              device, CWS_params)
                 else:      # (over the chunk as it runs: draw row j belongs to sweep row j)
                     waypoint_samples = _draw_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, n_goal, n_traj, obs_len, device,
                                                        use_TTST, use_CWS, rel_thresh, CWS_params)
@@ -141,6 +187,15 @@ def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template
                 ops.check_patch_status()      # (the ranking call waited for the chunk: a window that left the template raises here)
                 if perm is not None:
                     ops.check_gather_status()
+                if modes is not None:
+                    nan = ops.check_modes_status(raise_error=False)
+                    short = torch.nonzero(found["short"]).flatten().tolist()
+                    if short:
+                        raise RuntimeError(f"{name}: agent {b + short[0]}" + (f" (and {len(short) - 1} more)" if len(short) > 1 else "")
+                                           + f": fewer than the {modes[0]} modes asked for; its goal map holds "
+                                           + ("a NaN" if nan else "too few logits above -inf"))
+                    out["mode_mass"].append(found["mass"].gather(1, order.long()))      # (row r is mode order[:, r])
+                    out["mode_logit"].append(found["logit"].gather(1, order.long()))
     finally:
         model.train(was_training)
     return {k: (v[0] if len(v) == 1 else torch.cat(v)) for k, v in out.items()}
@@ -222,3 +277,37 @@ def predict_styles(bank, scene_image, observed, style, input_template, waypoints
                     max_effective_batch, forced_samples, return_maps, return_entropy=False)
     res["style_index"] = torch.from_numpy(style_index).to(res["scores"].device)
     return res
+
+
+def predict_modes(model, scene_image, observed, input_template, waypoints, n_modes, radius, obs_len, resize_factor, temperature,
+                  CWS_params=None, network=None, swap_semantic=False, batch_size=None, max_effective_batch=256, return_maps=False):
+    """The n_modes most likely futures of every agent of ONE scene, with no draw: a pure function of (weights, scene, observed steps).
+    No generator is read -- neither torch's nor NumPy's -- so two adapter sets can be compared forecast by forecast.
+
+    n_modes, radius  the goals are the modes of the goal map under greedy non-maximum suppression (ops.map_modes on the raw logits of
+                     the last way-point): the highest pixel, then the highest outside the disk of ``radius`` pixels around it, and
+                     so on; 1 <= n_modes <= 64, radius >= 0, and (n_modes - 1) * A(radius) < H * W (disk_area), below which finite
+                     logits always give n_modes modes
+    CWS_params       with several way-points: given, the intermediate ones are the expectation chain of cws_waypoints from every
+                     goal (deterministic); None, the top pixel of each intermediate plane's logits, shared by the modes
+    every other argument as for predict().
+    -> predict()'s results with K = n_modes (``trajectories``, ``waypoints``, ``scores``, ``order``, the maps with ``return_maps``;
+       mode m is sample m of the sweep) and ``mode_mass``, ``mode_logit`` [N, n_modes] in the ranked order (row r is mode
+       order[:, r]): the share of sigmoid(goal_map / T), normalised, that the mode claimed -- the masses of an agent are disjoint and
+       sum to the covered share of its map -- and the raw logit of its peak.  With one way-point ``order`` is 0 .. n_modes - 1.
+    An agent whose goal map gives fewer modes (non-finite logits) raises RuntimeError at the chunk's sync point.
+    Out of scope for now: a predict_styles form, evaluate() over modes, sub-pixel refinement of the peak, and capturing the call into
+    a hipGraph."""
+    n_modes, radius = int(n_modes), int(radius)
+    if not 1 <= n_modes <= MAX_SAMPLES:
+        raise ValueError(f"predict_modes: n_modes = {n_modes}; the ranking kernel takes 1 .. {MAX_SAMPLES}")
+    if radius < 0:
+        raise ValueError(f"predict_modes: radius = {radius} is negative")
+    use_CWS = CWS_params is not None
+    obs, waypoints, _, _, obs_len, _ = _validated("predict_modes", observed, scene_image, waypoints, n_modes, 1, obs_len, resize_factor, use_CWS,
+                                                  CWS_params, batch_size, None)
+    return _forecast("predict_modes", model, lambda: ops.refresh_filters(model), lambda b, n: (None, model.pred_features), scene_image, obs,
+                     input_template, waypoints, n_modes, 1, obs_len, resize_factor, temperature, use_TTST=False, use_CWS=use_CWS, rel_thresh=None,
+                     CWS_params=CWS_params, network=network, swap_semantic=swap_semantic, batch_size=batch_size,
+                     max_effective_batch=max_effective_batch, forced_samples=None, return_maps=return_maps, return_entropy=False,
+                     modes=(n_modes, radius))

@@ -225,6 +225,27 @@ int main() {
     EXPECT_REJECT(ynet_map_likelihood(cfp, 16, nullptr, 1, 1, 4, 4, 1.f, fp, fp, nullptr, &status, nullptr));            // nll without the ground truth
     EXPECT_REJECT(ynet_map_likelihood(cfp, 16, nullptr, 1, 1, 4, 4, 1.f, nullptr, fp, fp, &status, nullptr));            // hpd without the ground truth
     EXPECT_REJECT(ynet_map_likelihood(cfp, 16, cfp, 1, 1, 4, 4, 1.f, fp, fp, fp, nullptr, nullptr));                     // ground truth without a status flag
+    EXPECT_REJECT(ynet_map_modes(nullptr, 16, 1, 1, 4, 4, 20, 3, 1.f, fp, fp, fp, &status, &status, nullptr));           // no map
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 1, 4, 4, 20, 3, 1.f, nullptr, fp, fp, &status, &status, nullptr));          // no xy
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 1, 4, 4, 20, 3, 1.f, fp, nullptr, fp, &status, &status, nullptr));          // no logit
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 1, 4, 4, 20, 3, 1.f, fp, fp, fp, nullptr, &status, nullptr));               // no count
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 1, 4, 4, 20, 3, 1.f, fp, fp, fp, &status, nullptr, nullptr));               // no status flag
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 1, 4, 4, 0, 3, 1.f, fp, fp, fp, &status, &status, nullptr));                // n_modes outside 1 .. 64
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 1, 4, 4, 65, 3, 1.f, fp, fp, fp, &status, &status, nullptr));
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 1, 4, 4, 20, -1, 1.f, fp, fp, fp, &status, &status, nullptr));              // radius < 0
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 0, 1, 4, 4, 20, 3, 1.f, fp, fp, fp, &status, &status, nullptr));               // B, C, H, W < 1
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 0, 4, 4, 20, 3, 1.f, fp, fp, fp, &status, &status, nullptr));
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 1, 0, 4, 20, 3, 1.f, fp, fp, fp, &status, &status, nullptr));
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 1, 4, 0, 20, 3, 1.f, fp, fp, fp, &status, &status, nullptr));
+    EXPECT_REJECT(ynet_map_modes(cfp, 31, 2, 2, 4, 4, 20, 3, 1.f, fp, fp, fp, &status, &status, nullptr));               // batch stride below the image
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 1, 4, 4, 20, 3, 0.f, fp, fp, fp, &status, &status, nullptr));               // with mass: temperature 0
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 1, 4, 4, 20, 3, -1.f, fp, fp, fp, &status, &status, nullptr));
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 1, 4, 4, 20, 3, 1.f / 0.f, fp, fp, fp, &status, &status, nullptr));         // not finite
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 1, 4, 4, 20, 3, 0.f / 0.f, fp, fp, fp, &status, &status, nullptr));
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 1, 4, 4, 20, 3, 1e-39f, fp, fp, fp, &status, &status, nullptr));            // a denormal: 1 / T overflows
+    EXPECT_REJECT(ynet_map_modes(cfp, 1 << 20, 1, 1, 512, 513, 20, 3, 1.f, fp, fp, fp, &status, &status, nullptr));      // beyond YNET_MAP_MODES_MAX_PIXELS
+    EXPECT_REJECT(ynet_map_modes(cfp, 1ll << 40, 1, 1, 1 << 20, 1 << 20, 20, 3, 1.f, fp, fp, fp, &status, &status, nullptr));
+    EXPECT_REJECT(ynet_map_modes(cfp, 16, 1ll << 22, 1, 4, 4, 20, 3, 1.f, fp, fp, fp, &status, &status, nullptr));       // too many planes for one grid
     EXPECT_REJECT(ynet_resize_nearest(nullptr, (int*)dummy, 4, 4, 2, 2, 0.5, 0.5, nullptr));
     EXPECT_REJECT(ynet_resize_nearest((const int*)dummy, (int*)dummy, 4, 4, 2, 2, 0.0, 0.5, nullptr));      // factor 0
     EXPECT_REJECT(ynet_upconv_dgrad_ring(nullptr, 0, cfp, nullptr, 0, fp, 0, 1, 64, 32, 8, 8, nullptr));
