@@ -534,6 +534,28 @@ int ynet_sigmoid_temp(const float* x, float* y, long long B, int C, long long HW
 int ynet_map_likelihood(const float* x, long long batch_stride, const float* gt_xy, long long B, int C, int H, int W, float temperature,
                         float* nll, float* entropy, float* hpd, int* status, void* stream);
 
+/* The same nll and hpd at n_temps temperatures in ONE pass over the map (temperature scaling: choosing T of the distribution
+ * sigmoid(pred_goal_map / T) of utils/evaluate.py:128-131, which utils/image_utils.py:110-135 draws from, by the validation NLL; the
+ * reference hand-sets T).  Per plane (b, c) and temperature T_k, exactly as for ynet_map_likelihood: z = x / T_k, w = sigmoid(z),
+ * Z_k = sum w, g the rounded ground truth:
+ *   nll [n_temps][B][C] = log Z_k - log_sigmoid(z_g)
+ *   hpd [n_temps][B][C] = (sum over {i : x_i >= x_g} of w_i) / Z_k             membership on the raw fp32 logits: the same set at every k
+ * The entropy is not part of the sweep.  `temperatures` is a HOST array of n_temps values, read during the call: they travel, with
+ * their reciprocals, in the kernel's argument block, so the call reads no device memory besides x and gt_xy.  One launch, one workgroup
+ * per plane, the map read once; per pixel and temperature only the sigmoid is formed (fp32, as ynet_map_likelihood forms it), the sums
+ * and the two logs per plane and temperature are fp64, combined in a fixed order with no floating-point atomics: two runs give the
+ * same bits, and two equal temperatures of one call give equal entries.
+ * Rules, for every k separately: a NaN logit makes every entry of its plane NaN; a -inf logit adds 0 (g on it: nll = +inf, hpd = 1);
+ * sigmoids below fp32's range count as 0, so Z_k == 0 (entry k NaN) can happen at a small T_k where a larger one is finite.  A ground
+ * truth that rounds outside the map (or is NaN): NaN for all k, *status (device int, zero it first) becomes 1, nothing outside the
+ * map is read.  nll or hpd may be NULL, not both.
+ * Refused (non-zero, ynet_last_error) before any launch: null x, temperatures, gt_xy or status; n_temps outside
+ * 1 .. YNET_SWEEP_MAX_TEMPS; a temperature <= 0, not finite, or below 2.95e-39 (where 1 / T is not); B, C, H or W < 1;
+ * H * W > 2^31 - 2048; batch_stride < C * H * W; no output. */
+#define YNET_SWEEP_MAX_TEMPS 32
+int ynet_map_likelihood_sweep(const float* x, long long batch_stride, const float* gt_xy, long long B, int C, int H, int W,
+                              const float* temperatures, int n_temps, float* nll, float* hpd, int* status, void* stream);
+
 /* Deterministic goal modes of the goal map: greedy non-maximum suppression over the logits the goals are sampled from
  * (pred_goal_map, utils/evaluate.py:128-131; the reference has no deterministic multi-modal read-out: its soft-argmax is the mean of
  * the map).  Per plane (b, c) of x [B][C][H][W] (batch stride `batch_stride` elements, so a channel slice needs no copy), all

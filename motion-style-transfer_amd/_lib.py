@@ -133,6 +133,7 @@ SIGNATURES = {
     "ynet_pred_softargmax_workspace_floats": (c_ll, [c_ll, c_i, c_i]),
     "ynet_pred_softargmax": (c_i, [c_fp, c_ll, c_fp, c_fp, c_fp, c_fp, c_ll, c_i, c_i, c_i, c_i, c_fp]),
     "ynet_map_likelihood": (c_i, [c_fp, c_ll, c_fp, c_ll, c_i, c_i, c_i, c_f, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "ynet_map_likelihood_sweep": (c_i, [c_fp, c_ll, c_fp, c_ll, c_i, c_i, c_i, ctypes.POINTER(c_f), c_i, c_fp, c_fp, c_fp, c_fp]),
     "ynet_map_modes": (c_i, [c_fp, c_ll, c_ll, c_i, c_i, c_i, c_i, c_i, c_f, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "ynet_pad2d": (c_i, [c_fp, c_fp, c_ll, c_i, c_i, c_i, c_i, c_fp]),
     "ynet_seg_onehot_pad": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp]),

@@ -7,6 +7,7 @@
 // in flight per thread, as softargmax_plane (glue.hip) but without its row / column bookkeeping.  Per-pixel terms are fp32; the running
 // sums, the cross-wave combine and the final logs are fp64.  The public C ABI is include/ynet_hip.h.
 #include "ynet_common.h"
+#include "sigmoid_term.h"
 #include <math.h>
 
 namespace {
@@ -17,25 +18,12 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
-// z = x / T as sigmoid_temp_kernel (glue.hip) forms it for the sampler, in fp32: the product with 1 / T, corrected by its exact residual --
-// the correctly rounded quotient (almost always) in three operations instead of the ten of an IEEE division.
-template <bool DIVIDE>
-__device__ __forceinline__ float tempered(float x, float inv_t, float t) {
-    if (!DIVIDE) return x;
-    const float z = x * inv_t;
-    const float zc = __builtin_fmaf(__builtin_fmaf(-z, t, x), inv_t, z);
-    return (zc == zc) ? zc : z;        // (infinite x: the residual is NaN, the product is the answer)
-}
-
-// One logit in fp32.  With a = |z|, e = exp(-a), u = 1 + e:
+// One logit in fp32 (z and w: sigmoid_term.h, shared with temperature.hip).  With a = |z|, e = exp(-a), u = 1 + e:
 //   w = sigmoid(z) = 1 / u (z >= 0), e / u (z < 0);   log_sigmoid(z) = zmin - l1p,  zmin = min(z, 0),  l1p = log1p(e) = log(u) + (e - (u - 1)) / u
 // (the last term restores what the rounding of 1 + e dropped).  The two parts of log_sigmoid stay apart: zmin is exact and may be large,
 // l1p <= log 2 carries the rounding -- rounded into one fp32 number their sum would lose half an ulp of |z|, which a plane of a few
-// pixels (entropy ~ 0 as the difference of two numbers of that size) does not forgive.  e comes from v_exp_f32 on the rounded product
-// a * log2(e), corrected to first order by the product's exact residual.  a is clamped to 104 on the way: exp2 of -150 is 0 whatever
-// the denormal mode, so a -inf logit has e = 0 and w = 0 exactly and adds 0 to every sum (between 87.4 and 104 the sigmoid is below
-// fp32's normal range: a denormal or 0).  zmin is clamped to -FLT_MAX, so that 0 * -inf never forms.
-// A NaN comes out as w = 0 here; the caller tracks NaNs itself.
+// pixels (entropy ~ 0 as the difference of two numbers of that size) does not forgive.  zmin is clamped to -FLT_MAX, so that 0 * -inf
+// never forms.  A NaN comes out as w = 0 here; the caller tracks NaNs itself.
 struct Term {
     float w, zmin, l1p;
 };
@@ -43,18 +31,10 @@ struct Term {
 template <bool DIVIDE>
 __device__ __forceinline__ Term logit_term(float x, float inv_t, float t) {
     const float z = tempered<DIVIDE>(x, inv_t, t);
-    const float a = __builtin_fabsf(z);
-    const float L2E = 1.44269502162933349609375f, L2El = 1.925963033500011e-8f;      // log2(e) = L2E + L2El
-    const float ac = __builtin_fminf(a, 104.f);
-    const float p = -ac * L2E;
-    const float r = __builtin_fmaf(-ac, L2E, -p) - ac * L2El;
-    float e = __builtin_amdgcn_exp2f(p);
-    e = __builtin_fmaf(e, r * 0.693147182464599609375f, e);
-    const float u = 1.f + e;
-    const float ru = __builtin_amdgcn_rcpf(u);
+    const SigmoidTerm s = sigmoid_term(z);
     Term o;
-    o.l1p = __builtin_fmaf(__builtin_amdgcn_logf(u), 0.693147182464599609375f, (e - (u - 1.f)) * ru);
-    o.w = (z >= 0.f) ? ru : e * ru;
+    o.l1p = __builtin_fmaf(__builtin_amdgcn_logf(s.u), 0.693147182464599609375f, (s.e - (s.u - 1.f)) * s.ru);
+    o.w = sigmoid_weight(z, s);
     o.zmin = __builtin_amdgcn_fmed3f(z, -3.402823466e38f, 0.f);
     return o;
 }

@@ -321,6 +321,27 @@ class YNetTrainer:
         return avg_ade, avg_fde, list_metrics, list_trajs
 
     # ------------------------------------------------------------------------------------------
+    def calibrate_temperature(self, df_val, image_path, t_range=(0.25, 8.0), n_temps=16, rounds=2, steps="waypoints"):
+        """Temperature scaling (not in the reference, whose T is hand-set): the temperature of the goal-map distribution that minimises
+        the NLL of ``df_val``'s ground truth, found by a grid search over ``t_range`` (utils.calibrate.calibrate_temperature; data
+        prepared as for test()).  Prints the temperature, the NLL and the goal ECE before -> after, and returns the function's dict.
+        ``self.params["temperature"]`` is NOT changed: the caller decides."""
+        return self._calibrate_temperature(df_val, image_path, t_range=t_range, n_temps=n_temps, rounds=rounds, steps=steps, **self.params)
+
+    def _calibrate_temperature(self, df_val, image_path, dataset_name, resize_factor, batch_size, obs_len, pred_len, waypoints, temperature,
+                               t_range, n_temps, rounds, steps, use_raw_data=False, network=None, swap_semantic=False, **kwargs):
+        from ..utils.calibrate import calibrate_temperature, check_arguments
+        check_arguments(waypoints, temperature, t_range, n_temps, rounds, steps)      # (before any data or model is touched)
+        val_images, val_loader, _ = self.prepare_data(df_val, image_path, dataset_name, "test", obs_len, pred_len, resize_factor, use_raw_data)
+        model = self.model.to(self.device)
+        out = calibrate_temperature(model, val_loader, val_images, self.device, self.templates(), waypoints, obs_len, batch_size, resize_factor,
+                                    temperature, t_range=t_range, n_temps=n_temps, rounds=rounds, steps=steps, network=network,
+                                    swap_semantic=swap_semantic)
+        print(f"Calibrated temperature: {out['temperature']} (was {temperature}" + (", at the boundary of t_range" if out["at_boundary"] else "")
+              + f") \nVal NLL: {out['nll_before']} -> {out['nll']} \nVal goal ECE: {out['ece_before']} -> {out['ece']}")
+        return out
+
+    # ------------------------------------------------------------------------------------------
     def predict(self, df_obs, image_path_or_images, return_maps=False):
         """Forecasts WITHOUT ground truth (new; the reference's test() needs obs_len + pred_len rows per agent and its plotting
         helpers re-run it): the K = n_goal * n_traj sampled futures of every agent, scored against the goal map and ranked

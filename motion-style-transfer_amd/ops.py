@@ -2834,6 +2834,57 @@ def map_likelihood(x: torch.Tensor, gt_xy=None, temperature: float = 1.0, want: 
     return out
 
 
+SWEEP_OUTPUTS = ("nll", "hpd")
+SWEEP_MAX_TEMPS = 32      # YNET_SWEEP_MAX_TEMPS of include/ynet_hip.h
+
+
+def sweep_temperatures(temperatures, what: str = "map_likelihood_sweep") -> np.ndarray:
+    """A host sequence of temperatures as the sweep kernel takes them: a contiguous fp32 array of 1 .. SWEEP_MAX_TEMPS positive, finite
+    values (with finite reciprocals); anything else is refused."""
+    if torch.is_tensor(temperatures):
+        if temperatures.is_cuda:
+            raise TypeError(f"{what}: the temperatures are read on the host at call time; pass a host sequence, not a device tensor")
+        temperatures = temperatures.detach().numpy()
+    t64 = np.asarray(temperatures, dtype=np.float64).reshape(-1)
+    if not 1 <= t64.size <= SWEEP_MAX_TEMPS:
+        raise ValueError(f"{what}: {t64.size} temperatures, expected 1 .. {SWEEP_MAX_TEMPS}")
+    with np.errstate(over="ignore", divide="ignore"):
+        t = np.ascontiguousarray(t64.astype(np.float32))
+        ok = np.isfinite(t) & (t > 0) & np.isfinite(np.float32(1.0) / np.where(t > 0, t, np.float32(1.0)))
+    if not ok.all():
+        raise ValueError(f"{what}: temperature {t64[int(np.argmin(ok))]!r} (entry {int(np.argmin(ok))}) must be positive and finite in fp32")
+    return t
+
+
+def map_likelihood_sweep(x: torch.Tensor, gt_xy: torch.Tensor, temperatures, want: Sequence[str] = SWEEP_OUTPUTS):
+    """map_likelihood's nll and hpd at every temperature of a host sequence in ONE pass over x (ynet_map_likelihood_sweep; temperature
+    scaling of the distribution of utils/evaluate.py:128-131, utils/image_utils.py:110-135, which the reference hand-sets): per plane of
+    x [B, C, H, W] and temperature T_k, p = sigmoid(x / T_k) normalised to sum 1.  gt_xy [B, C, 2] (x, y) = (column, row) device
+    coordinates, rounded half-even to a pixel g.  ``temperatures``: 1 .. 32 positive finite values on the host (list, array or host
+    tensor), converted to fp32.
+    -> dict of [n_T, B, C] device tensors, one per name in ``want``: "nll" = -log p_g (nats), "hpd" = the mass of {p >= p_g}, membership
+    decided on the raw logits.  A channel view such as x[:, 1:3] is read in place.  Not differentiable.  A ground truth outside the map
+    gives NaN at every temperature for its plane and raises at the next check_likelihood_status()."""
+    want = tuple(want)
+    if not want or len(set(want)) != len(want) or any(w not in SWEEP_OUTPUTS for w in want):
+        raise ValueError(f"map_likelihood_sweep: want {want!r}: a non-empty selection of {SWEEP_OUTPUTS} is expected")
+    temps = sweep_temperatures(temperatures)
+    t, c, bs = _plane_desc(x.detach() if torch.is_tensor(x) else x, "map_likelihood_sweep")
+    B, _, H, W = t.shape
+    dev = t.device
+    _need_gpu(gt_xy, "map_likelihood_sweep gt_xy", dtypes=(torch.float32, torch.float64))
+    if tuple(gt_xy.shape) != (B, c, 2):
+        raise ValueError(f"map_likelihood_sweep: gt_xy {tuple(gt_xy.shape)} does not go with the map {tuple(t.shape)} (expected {(B, c, 2)})")
+    gt = gt_xy.detach().float().contiguous()
+    st = _status_flag(_likelihood_status, dev)
+    out = {w: torch.empty((temps.size, B, c), device=dev, dtype=torch.float32) for w in want}
+    ptr = {w: (out[w].data_ptr() if w in out else None) for w in SWEEP_OUTPUTS}
+    lib = _lib()
+    L.check(lib.ynet_map_likelihood_sweep(t.data_ptr(), bs, gt.data_ptr(), B, c, H, W, temps.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                          int(temps.size), ptr["nll"], ptr["hpd"], st.data_ptr(), _stream()), lib)
+    return out
+
+
 def check_likelihood_status(raise_error: bool = True) -> bool:
     """Raise if a map_likelihood call met a ground truth that rounds outside its map (checked at a sync point); the flag is cleared.
     raise_error=False: report it instead (-> True if one did) -- evaluate() keeps such a plane's NaN nll / hpd and warns."""

@@ -225,6 +225,38 @@ int main() {
     EXPECT_REJECT(ynet_map_likelihood(cfp, 16, nullptr, 1, 1, 4, 4, 1.f, fp, fp, nullptr, &status, nullptr));            // nll without the ground truth
     EXPECT_REJECT(ynet_map_likelihood(cfp, 16, nullptr, 1, 1, 4, 4, 1.f, nullptr, fp, fp, &status, nullptr));            // hpd without the ground truth
     EXPECT_REJECT(ynet_map_likelihood(cfp, 16, cfp, 1, 1, 4, 4, 1.f, fp, fp, fp, nullptr, nullptr));                     // ground truth without a status flag
+    {   // the sweep reads its temperatures on the host: exactly n_temps of them (a heap array of that length, so a read past it is seen)
+        float* t32 = new float[YNET_SWEEP_MAX_TEMPS];
+        float* t3 = new float[3];
+        for (int k = 0; k < YNET_SWEEP_MAX_TEMPS; ++k) t32[k] = 0.25f + 0.25f * k;
+        t3[0] = 1.f, t3[1] = 1.8f, t3[2] = 0.f;
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 16, cfp, 0, 1, 4, 4, t32, YNET_SWEEP_MAX_TEMPS, fp, fp, &status, nullptr));      // B < 1, found after all 32 were read
+        EXPECT_REJECT(ynet_map_likelihood_sweep(nullptr, 16, cfp, 1, 1, 4, 4, t32, YNET_SWEEP_MAX_TEMPS, fp, fp, &status, nullptr));  // no map
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 16, cfp, 1, 1, 4, 4, nullptr, 3, fp, fp, &status, nullptr));            // no temperatures
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 16, cfp, 1, 1, 4, 4, t32, 0, fp, fp, &status, nullptr));                // n_temps outside 1 .. 32
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 16, cfp, 1, 1, 4, 4, t32, YNET_SWEEP_MAX_TEMPS + 1, fp, fp, &status, nullptr));
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 16, cfp, 1, 1, 4, 4, t3, 3, fp, fp, &status, nullptr));                 // the last of three is 0
+        t3[2] = -1.f;
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 16, cfp, 1, 1, 4, 4, t3, 3, fp, fp, &status, nullptr));
+        t3[2] = 1.f / 0.f;
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 16, cfp, 1, 1, 4, 4, t3, 3, fp, fp, &status, nullptr));                 // not finite
+        t3[2] = 0.f / 0.f;
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 16, cfp, 1, 1, 4, 4, t3, 3, fp, fp, &status, nullptr));
+        t3[2] = 1e-39f;
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 16, cfp, 1, 1, 4, 4, t3, 3, fp, fp, &status, nullptr));                 // a denormal: 1 / T overflows
+        t3[2] = 2.5f;
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 1ll << 31, cfp, 1, 1, 32768, 65536, t3, 3, fp, fp, &status, nullptr));  // 2^31 pixels per plane
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 16, cfp, 0, 1, 4, 4, t3, 3, fp, fp, &status, nullptr));                 // B, C, H, W < 1
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 16, cfp, 1, 0, 4, 4, t3, 3, fp, fp, &status, nullptr));
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 16, cfp, 1, 1, 0, 4, t3, 3, fp, fp, &status, nullptr));
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 16, cfp, 1, 1, 4, 0, t3, 3, fp, fp, &status, nullptr));
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 31, cfp, 2, 2, 4, 4, t3, 3, fp, fp, &status, nullptr));                 // batch stride below the image
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 16, cfp, 1, 1, 4, 4, t3, 3, nullptr, nullptr, &status, nullptr));       // no output
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 16, nullptr, 1, 1, 4, 4, t3, 3, fp, fp, &status, nullptr));             // no ground truth
+        EXPECT_REJECT(ynet_map_likelihood_sweep(cfp, 16, cfp, 1, 1, 4, 4, t3, 3, fp, fp, nullptr, nullptr));                 // no status flag
+        delete[] t32;
+        delete[] t3;
+    }
     EXPECT_REJECT(ynet_map_modes(nullptr, 16, 1, 1, 4, 4, 20, 3, 1.f, fp, fp, fp, &status, &status, nullptr));           // no map
     EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 1, 4, 4, 20, 3, 1.f, nullptr, fp, fp, &status, &status, nullptr));          // no xy
     EXPECT_REJECT(ynet_map_modes(cfp, 16, 1, 1, 4, 4, 20, 3, 1.f, fp, nullptr, fp, &status, &status, nullptr));          // no logit
