@@ -54,6 +54,12 @@ int ynet_pack_weight(const float* w, float* wp, int cout, int cin, int K, int mo
  *   cin = sum(src_c), cout = sum(dst_c); wp packed for (cout, cin); bias [cout] or NULL
  *   workspace: optional scratch of ynet_conv2d_workspace_floats(B, H, W, cout) floats (may be NULL / 0):
  *   lets small-map launches (8^2 .. 32^2) split their input-channel loop over more workgroups.
+ * Alignment: ynet_conv2d and ynet_conv2d_wgrad serve sources, mask, dy and destinations at ANY 4-byte address and any batch
+ *   stride; the LDS-DMA / streaming kernels need every plane on a 16-byte boundary (pointer % 16 == 0, batch stride % 4 == 0,
+ *   W % 4 == 0), anything else takes the register-staged tiles (same results within rounding, slower).  The epilogue variants
+ *   below exist in the LDS-DMA kernels only: ynet_conv2d_pool, ynet_conv2d_add, ynet_conv2d_relu_bits and
+ *   ynet_conv2d_dgrad_relu_bits REFUSE a source, mask, destination or addend off that boundary, and ynet_conv2d_dgrad_relu a
+ *   relu_of off it, before anything is launched (the message names the operand).  INTEGRATION.md has the table.
  */
 long long ynet_conv2d_workspace_floats(int B, int H, int W, int cout);
 int ynet_conv2d(const float* const* src, const int* src_c, const long long* src_bs, const int* src_bmod, int nsrc,
@@ -61,6 +67,13 @@ int ynet_conv2d(const float* const* src, const int* src_c, const long long* src_
                 float* const* dst, const int* dst_c, const long long* dst_bs, int ndst,
                 int B, int H, int W, int K, int relu, float* workspace, long long workspace_floats,
                 void* stream);
+/* Which kernel the dispatcher of ynet_conv2d and its variants (which = 0) or of ynet_conv2d_wgrad (which = 1) launched last in this process
+ * (on any thread: autograd runs a backward pass on its own); the value is taken (the next call returns 0 until another launch).  For tests and
+ * profiles: the choice depends on operand alignment, which ynet_conv2d_plan does not see.
+ *   which 0: bits 0..3 the kernel (1 register-staged tiles, 2 LDS-DMA row tiles, 3 LDS-DMA folded tiles, 4 1x1 streaming), bits 4..7 rows per
+ *            wave, bits 8..11 the split of the input-channel loop, bit 12 / 13: 16-byte loads / stores were legal for the operands.
+ *   which 1: 1 register-staged 4-row tiles, 2 two-row LDS-DMA tiles, 3 rolling-row LDS-DMA strips, 4 1x1 streaming. */
+int ynet_conv2d_last_launch(int which);
 /* ynet_conv2d with ONE destination plus its 2 x 2 max-pooled copy written by the same epilogue: the last convolution of an encoder
  * stage and the nn.MaxPool2d(2, 2) that opens the next one (models/ynet.py:202,215) without the stand-alone pass over y.
  * pooled [B][cout][H/2][W/2] (batch stride pooled_bs), the first-maximum / NaN rule of ynet_maxpool2_fwd; H, W even.

@@ -3,6 +3,8 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <atomic>
+
 static thread_local char g_err[512] = "";
 
 void ynet_set_error(const char* fmt, ...) {
@@ -20,6 +22,14 @@ int ynet_check_launch(const char* what) {
     }
     return 0;
 }
+
+// What the dispatchers of ynet_conv2d (slot 0) and ynet_conv2d_wgrad (slot 1) launched last (include/ynet_hip.h: ynet_conv2d_last_launch): the
+// launchers note it, a reader takes it and leaves 0.  One record per process, not per thread: autograd runs a backward pass on a thread of its own.
+static std::atomic<int> g_launch[2];
+
+void ynet_note_launch(int which, int code) { g_launch[which & 1].store(code, std::memory_order_relaxed); }
+
+extern "C" int ynet_conv2d_last_launch(int which) { return g_launch[which & 1].exchange(0, std::memory_order_relaxed); }
 
 extern "C" const char* ynet_last_error(void) { return g_err; }
 extern "C" int ynet_abi_version(void) { return 1; }

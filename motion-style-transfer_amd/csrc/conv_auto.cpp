@@ -115,7 +115,7 @@ int make_plan(const YnetConvAuto* a, Plan& p) {
     }
     if (a->addend) {      // y = [relu](conv(cat(src)) + bias + addend[b % mod]) (utils/evaluate.py:248-283)
         YNET_REQUIRE(a->ndst == 1 && !a->mask && !a->relu_of && !a->pooled, "conv2d_auto: addend takes one destination and no mask / relu_of / pooled");
-        const bool ok = !(a->flags & YNET_AUTO_NO_WINOGRAD) && K == 3 && srcs_aligned(a) && al(a->addend, 8) && al(a->dst[0], 8) && !(a->dst_bs[0] & 1) && a->nsrc <= 3;
+        const bool ok = !(a->flags & YNET_AUTO_NO_WINOGRAD) && K == 3 && srcs_aligned(a) && al(a->addend, 8) && !(a->addend_bs & 1) && al(a->dst[0], 8) && !(a->dst_bs[0] & 1) && a->nsrc <= 3;
         bool plain = true;      // (the Winograd kernels take no per-source batch modulus)
         for (int i = 0; i < a->nsrc; ++i) plain = plain && a->src_bmod[i] <= 0;
         if (ok && plain && ctot == 32 && ynet_conv2d_winograd_cat_supported(B, H, W, cs, a->nsrc, ctot, K)) {

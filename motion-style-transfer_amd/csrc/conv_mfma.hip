@@ -1301,6 +1301,7 @@ static int launch_conv_m(ConvArgs& a, hipStream_t st) {
         slots = per_cu * cus;
     }
     const long long nblk = nt < slots ? nt : slots;
+    ynet_note_launch(0, 1 | (R << 4) | (a.ksplit << 8) | (a.vec_load << 12) | (a.vec_store << 13));
     hipLaunchKernelGGL((conv_mfma_kernel<KS, NCB, R, CC, MASK, M16>), dim3((unsigned)nblk), dim3(256), C::LDS_BYTES, st, a);
     if (a.ksplit > 1) {
         SplitReduceArgs r{};
@@ -1401,6 +1402,7 @@ static int launch_dma_m(ConvArgs& a, hipStream_t st) {
         slots = per_cu * cus;
     }
     const long long nblk = nt < slots ? nt : slots;
+    ynet_note_launch(0, (FOLD > 1 ? 3 : 2) | (R << 4) | (a.ksplit << 8) | (a.vec_load << 12) | (a.vec_store << 13));
     hipLaunchKernelGGL((KERNEL), dim3((unsigned)nblk), dim3(256), C::LDS_BYTES, st, a);
     if (a.ksplit > 1) {
         SplitReduceArgs r{};
@@ -1604,6 +1606,7 @@ static int launch_conv1x1_stream(const ConvArgs& a, hipStream_t st) {
     k.hw4 = (long long)a.H * a.W / 4;
     long long blocks = ((long long)a.B * k.hw4 * (4 / PX) + 255) / 256;
     if (blocks > 16384) blocks = 16384;
+    ynet_note_launch(0, 4 | (1 << 8) | (a.vec_load << 12) | (a.vec_store << 13));
     hipLaunchKernelGGL((conv1x1_stream_kernel<CT, PX>), dim3((unsigned)blocks), dim3(256), 0, st, k);
     return ynet_check_launch("conv2d(1x1)");
 }
@@ -1879,7 +1882,7 @@ static int conv2d_impl(const float* const* src, const int* src_c, const long lon
     a.emask_bs = emask_bs;
     if (emask != nullptr) {
         YNET_REQUIRE(a.ndst == 1 && a.dst[0].p != nullptr && addend == nullptr, "conv2d: the output-side ReLU mask needs exactly one destination");
-        YNET_REQUIRE((reinterpret_cast<uintptr_t>(emask) & 15) == 0 && (emask_bs & 3) == 0, "conv2d: the output-side ReLU mask must be 16-byte aligned");
+        YNET_REQUIRE((reinterpret_cast<uintptr_t>(emask) & 15) == 0 && (emask_bs & 3) == 0, "conv2d_dgrad_relu: relu_of (the output-side ReLU mask) must be 16-byte aligned with a batch stride that is a multiple of 4 floats");
     }
     a.wp = wp;
     a.bias = bias;
@@ -1896,6 +1899,20 @@ static int conv2d_impl(const float* const* src, const int* src_c, const long lon
     for (int i = 0; i < a.nsrc; ++i)
         if ((reinterpret_cast<uintptr_t>(a.src[i].p) & 15) || (a.src[i].bs & 3)) a.vec_load = 0;
     if (mask && ((reinterpret_cast<uintptr_t>(mask) & 15) || (mask_bs & 3))) a.vec_load = 0;
+    if ((W % 4) == 0 && (pool != nullptr || bits_out != nullptr || bits_in != nullptr || addend != nullptr)) {
+        // The pooled copy, the 1-bit masks and the additive term exist in the LDS-DMA kernels only.  An operand off a 16-byte boundary would
+        // send the call to the register-staged tiles, which write dst and only then find the epilogue missing: refuse it HERE, before any launch.
+        const char* what = pool ? "conv2d_pool" : (addend ? "conv2d_add" : "conv2d (bit mask)");
+        for (int i = 0; i < a.nsrc; ++i)
+            YNET_REQUIRE(!(reinterpret_cast<uintptr_t>(a.src[i].p) & 15) && !(a.src[i].bs & 3),
+                         "%s: source %d must be 16-byte aligned with a batch stride that is a multiple of 4 floats", what, i);
+        YNET_REQUIRE(!mask || (!(reinterpret_cast<uintptr_t>(mask) & 15) && !(mask_bs & 3)),
+                     "%s: the mask must be 16-byte aligned with a batch stride that is a multiple of 4 floats", what);
+        YNET_REQUIRE(!(reinterpret_cast<uintptr_t>(a.dst[0].p) & 15) && !(a.dst[0].bs & 3),
+                     "%s: the destination must be 16-byte aligned with a batch stride that is a multiple of 4 floats", what);
+        YNET_REQUIRE(!addend || (!(reinterpret_cast<uintptr_t>(addend) & 15) && !(addend_bs & 3)),
+                     "%s: the additive term (addend) must be 16-byte aligned with an image stride that is a multiple of 4 floats", what);
+    }
     return conv_dispatch(a, K, (hipStream_t)stream);
 }
 

@@ -1206,6 +1206,7 @@ static int launch_wgrad_m(WgradArgs& a, float* dw, float* db, hipStream_t st) {
         attr_set = true;
     }
     const long long nblk = (long long)a.nsplit * a.co_blks * a.ci_blks;
+    ynet_note_launch(1, 1);
     hipLaunchKernelGGL((wgrad_mfma_kernel<KS, MASK>), dim3((unsigned)nblk), dim3(256), C::LDS_BYTES, st, a);
     int rc = ynet_check_launch("conv2d_wgrad");
     if (rc) return rc;
@@ -1243,6 +1244,7 @@ static int launch_wgrad_dma(WgradArgs& a, float* dw, float* db, hipStream_t st) 
     (void)hipMemsetAsync(prof_dev, 0, 64, st);
     a.prof = prof_dev;
 #endif
+    ynet_note_launch(1, 2);
     hipLaunchKernelGGL((wgrad_dma_kernel<MASK, TH_>), dim3((unsigned)nblk), dim3(256), C::LDS_BYTES, st, a);
 #ifdef YNET_WG_PROFILE
     {
@@ -1296,6 +1298,7 @@ static int launch_wgrad1x1_stream(WgradArgs& a, float* dw, float* db, float* wor
     a.nsplit = grid;
     a.partial_w = k.partial_w = workspace;
     a.partial_b = k.partial_b = db ? workspace + (long long)grid * a.cout * 32 : nullptr;
+    ynet_note_launch(1, 4);
     if (a.cout <= 16) hipLaunchKernelGGL(wgrad1x1_stream_kernel<1>, dim3(grid), dim3(256), 0, st, k);
     else hipLaunchKernelGGL(wgrad1x1_stream_kernel<2>, dim3(grid), dim3(256), 0, st, k);
     int rc = ynet_check_launch("conv2d_wgrad(1x1)");
@@ -1326,6 +1329,7 @@ static int launch_wgrad_roll(WgradArgs& a, float* dw, float* db, hipStream_t st)
         (void)hipEventCreate(&e1);
         (void)hipEventRecord(e0, st);
     }
+    ynet_note_launch(1, 3);
     hipLaunchKernelGGL((wgrad_roll_kernel<MASK>), dim3((unsigned)nblk), dim3(256), C::LDS_BYTES, st, a);
     if (timing) {
         (void)hipEventRecord(e1, st);

@@ -24,6 +24,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 void ynet_set_error(const char* fmt, ...);
 int ynet_check_launch(const char* what);
+void ynet_note_launch(int which, int code);      // (ynet_conv2d_last_launch: which 0 = ynet_conv2d's kernels, 1 = ynet_conv2d_wgrad's)
 
 #define YNET_REQUIRE(cond, ...)              \
     do {                                     \

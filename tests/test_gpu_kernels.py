@@ -21,8 +21,9 @@ def close(got, want, rtol=2e-5, atol=2e-5, scale_rel=None, msg=""):
     if scale_rel is not None:
         atol = max(atol, scale_rel * float(want.abs().max()))
     err = (got - want).abs()
-    bad = err > atol + rtol * want.abs()
-    assert not bool(bad.any()), f"{msg}: max err {float(err.max()):.3e} (atol {atol:.2e}), {int(bad.sum())} bad of {bad.numel()}"
+    # (NaN-safe: an error that is not <= the bound is bad -- `err > bound` is False for a NaN; an element that is NaN on both sides counts as equal)
+    bad = ~(err <= atol + rtol * want.abs()) & ~(torch.isnan(got) & torch.isnan(want))
+    assert not bool(bad.any()), f"{msg}: max err {float(torch.nan_to_num(err, nan=float('inf')).max()):.3e} (atol {atol:.2e}), {int(bad.sum())} bad of {bad.numel()}"
 
 
 def rnd(*shape, seed=0, scale=1.0):
@@ -1566,16 +1567,26 @@ def test_pred_softargmax_is_conv1x1_then_softargmax(dev, B, cin, cout, H, W, sca
 
 def test_pred_softargmax_nonfinite_and_unsupported(dev):
     ops = pkg("ops")
-    x = F.relu(rnd(1, 32, 16, 32, seed=5))
+    # The reference is the composition itself, SoftArgmax2D(conv1x1(x)) in stock fp32 torch.  A non-finite INPUT reaches every plane of its pixel (0 * inf = NaN in
+    # the predictor's product, on the matrix cores as in F.conv2d), so the -inf / +inf logits of single planes come from an overflowing product, and the NaN
+    # input sits in an image of its own.  (Until close() counted NaN as a mismatch this test took the input channels for the logits and passed on NaN output.)
+    x = F.relu(rnd(2, 32, 16, 32, seed=5))
     w = torch.zeros(4, 32, 1, 1)
-    w[0, 0] = w[1, 1] = w[2, 2] = w[3, 3] = 1.0                      # logits of plane c = input channel c
-    x[0, 0, 3, 5] = float("-inf")
-    x[0, 1, 2, 7] = float("nan")
-    x[0, 2, 9, 9] = float("inf")
-    want = O.softargmax2d(x[:, :4])
+    w[0, 0] = w[1, 1] = w[2, 2] = w[3, 3] = 2.0                      # logits of plane c = 2 * input channel c
+    x[0, 0, 3, 5] = -3e38                                            # 2 * -3e38 = -inf in plane 0: its weight is 0, the plane stays finite
+    x[0, 2, 9, 9] = 3e38                                             # +inf in plane 2: exp(inf - inf) = NaN, as in the reference
+    x[1, 1, 2, 7] = float("nan")                                     # image 1: a NaN input -> every plane
+    logits = F.conv2d(x, w)
+    assert logits[0, 0, 3, 5] == float("-inf") and logits[0, 2, 9, 9] == float("inf") and bool(torch.isfinite(logits[0, [1, 3]]).all())
+    want = O.softargmax2d(logits)
     got = ops.pred_softargmax(x.to(dev), w.to(dev), None).cpu()
-    assert torch.isnan(got[0, 1]).all() and torch.isnan(got[0, 2]).all() and torch.isnan(want[0, 1]).all()
-    close(got[0, [0, 3]], want[0, [0, 3]], rtol=1e-5, atol=2e-5, msg="planes with -inf / finite logits")
+    assert torch.isnan(got[0, 2]).all() and torch.isnan(want[0, 2]).all() and torch.isnan(got[1]).all() and torch.isnan(want[1]).all()
+    assert bool(torch.isfinite(want[0, [0, 1, 3]]).all())
+    close(got[0, [0, 1, 3]], want[0, [0, 1, 3]], rtol=1e-5, atol=2e-5, msg="planes with -inf / finite logits")
+    # non-finite inputs in one image: every plane of that image is NaN, in the composition and in the kernel
+    x = F.relu(rnd(1, 32, 16, 32, seed=5))
+    x[0, 0, 3, 5], x[0, 1, 2, 7], x[0, 2, 9, 9] = float("-inf"), float("nan"), float("inf")
+    assert torch.isnan(O.softargmax2d(F.conv2d(x, w))).all() and torch.isnan(ops.pred_softargmax(x.to(dev), w.to(dev), None)).all()
     assert not ops.pred_softargmax_supported(torch.zeros(1, 32, 17, 23, device=dev), w.to(dev))      # H*W % 128 != 0
     assert not ops.pred_softargmax_supported(torch.zeros(1, 24, 16, 32, device=dev), torch.zeros(4, 24, 1, 1, device=dev))
     assert not ops.pred_softargmax_supported(torch.zeros(1, 32, 16, 32, device=dev), torch.zeros(33, 32, 1, 1, device=dev))
