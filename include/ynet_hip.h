@@ -620,9 +620,15 @@ int ynet_heatmap_analytic(const float* xy, float* out, int N, int H, int W, int 
  * P independent sets of N 2-D points with integer-valued coordinates (sampled pixels), K clusters each.
  * points [P][N][2] fp32, init_idx [P][K] = indices of the initial centres (the host draws them with
  * np.random.choice, keeping the reference's RNG stream), centers [P][K][2] out.  Stops when (sum of centre
- * shifts)^2 < tol or after iter_limit iterations (0 = no limit).  status[p] = (iterations << 8) | empty, where
- * empty = 1 means a cluster lost all its points (the reference then re-seeds it with torch.randint): the centres of
- * that set are undefined and the caller must redo it on the host path.  N <= 18000, K <= 32. */
+ * shifts)^2 < tol or after iter_limit iterations; iter_limit == 0 means "until converged" and needs tol > 0.
+ * status[p] = (iterations << 8) | flags:
+ *   bit 0 (value 1): a cluster lost all its points (the reference then re-seeds it with torch.randint): the centres of
+ *     that set are undefined and the caller must redo it on the host path;
+ *   bit 1 (value 2): an init_idx entry of that set lies outside 0 .. N-1 (a caller bug).  The entry is never used as an
+ *     address; the set runs no iteration (iterations = 0) and its centres are NaN.  The other sets of the call are served.
+ * N <= 18000, K <= 32, K <= N.
+ * Refused (non-zero, ynet_last_error) before any launch: a null pointer; P < 1; N, K outside those limits; iter_limit < 0;
+ * iter_limit == 0 with a tol that is not > 0 (zero, negative or NaN: the iteration could not end). */
 int ynet_kmeans2d(const float* points, const int* init_idx, float* centers, int* status, int P, int N, int K, float tol,
                   int iter_limit, void* stream);
 

@@ -1183,7 +1183,9 @@ __global__ __launch_bounds__(256) void heatmap_analytic_kernel(const float* __re
 //   update:  c_j = sum_j / n_j (one fp32 division per coordinate)          (selected.mean(dim=0))
 //   stop:    (sum_j sqrt(fl(ddx^2 + ddy^2)))^2 < tol, or iter_limit         (center_shift ** 2 < tol)
 // An empty cluster needs the reference's torch.randint re-seed: the kernel reports it (status 1) and the host
-// runs that person on its slow path.
+// runs that person on its slow path.  An init_idx entry outside 0 .. N-1 is never used as an LDS index: that person
+// runs no iteration, gets NaN centres and status 2.  iter_limit == 0 runs until the shift test passes, which needs
+// tol > 0 (the host entry refuses the call otherwise: the loop could not end).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void kmeans2d_kernel(const float* __restrict__ points, const int* __restrict__ init_idx,
                                                         float* __restrict__ centers, int* __restrict__ status, int N, int K,
@@ -1201,13 +1203,29 @@ __global__ __launch_bounds__(1024) void kmeans2d_kernel(const float* __restrict_
         px[i] = (int)rintf(P[2 * i]);
         py[i] = (int)rintf(P[2 * i + 1]);
     }
+    if (tid == 0) {
+        flag[0] = 0;
+        flag[1] = 0;
+    }
     __syncthreads();
     if (tid < K) {
-        const int j = init_idx[person * K + tid];
-        cx[tid] = (float)px[j];
-        cy[tid] = (float)py[j];
+        const int j = init_idx[(long long)person * K + tid];
+        if (j < 0 || j >= N) {
+            flag[0] = 3;      // (every thread that sees a bad entry writes the same value)
+        } else {
+            cx[tid] = (float)px[j];
+            cy[tid] = (float)py[j];
+        }
     }
-    if (tid == 0) flag[0] = 0;
+    __syncthreads();
+    if (flag[0] == 3) {      // the same for the whole workgroup: it leaves as one, before any iteration
+        if (tid < K) {
+            centers[((long long)person * K + tid) * 2] = NAN;
+            centers[((long long)person * K + tid) * 2 + 1] = NAN;
+        }
+        if (tid == 0) status[person] = 2;
+        return;
+    }
     int it = 0;
     for (;;) {
         if (tid < 3 * K) sums[tid] = 0;
@@ -2061,6 +2079,9 @@ int ynet_kmeans2d(const float* points, const int* init_idx, float* centers, int*
                   int iter_limit, void* stream) {
     YNET_REQUIRE(points && init_idx && centers && status, "kmeans2d: null pointer");
     YNET_REQUIRE(P > 0 && N > 0 && N <= 18000 && K >= 1 && K <= 32 && K <= N, "kmeans2d: bad shape P=%d N=%d K=%d (N <= 18000, K <= 32)", P, N, K);
+    YNET_REQUIRE(iter_limit >= 0, "kmeans2d: iter_limit = %d must be >= 0 (0 = until converged)", iter_limit);
+    YNET_REQUIRE(tol > 0.f || iter_limit != 0, "kmeans2d: tol = %g with iter_limit == 0 cannot end (tol must be > 0 when iter_limit == 0)",
+                 (double)tol);
     const int lds = (2 * N + 64 + 96 + 2) * 4;
     static bool attr_dev[YNET_MAX_DEV] = {false};
     bool& attr_set = attr_dev[ynet_device_slot()];

@@ -2598,7 +2598,10 @@ def rot_coords(xy: torch.Tensor, center, matrix, offset) -> torch.Tensor:
 def kmeans2d(points: torch.Tensor, init_idx: torch.Tensor, tol: float = 1e-3, iter_limit: int = 1000):
     """Lloyd's k-means of P independent point sets on the device (one workgroup per set; TTST).
     points [P,N,2] fp32 with integer-valued coordinates, init_idx [P,K] int32 -> (centers [P,K,2], status [P] int32:
-    bit 0 = a cluster went empty (centres undefined, redo on the host path), bits 8.. = iterations)."""
+    bit 0 = a cluster went empty (centres undefined, redo on the host path), bit 1 = an init_idx entry of that set lies
+    outside 0 .. N-1 (no iteration, NaN centres), bits 8.. = iterations).  Stops when (sum of centre shifts)^2 < tol or
+    after iter_limit iterations; iter_limit == 0 means "until converged" and needs tol > 0.  iter_limit < 0, and
+    iter_limit == 0 with tol <= 0 or NaN, are refused (RuntimeError) before any launch."""
     _need_gpu(points, "kmeans2d points")
     P, N, _ = points.shape
     K = init_idx.shape[1]

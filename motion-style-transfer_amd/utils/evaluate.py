@@ -409,7 +409,9 @@ def ttst_goals(model, wp_sigmoid_last, wp_logits_last, n_goal, rel_thresh, draw=
     """Test-time sampling trick (utils/evaluate.py:134-161): 10000 thresholded goal samples per person (with
     replacement) clustered into n_goal - 1 centres by ``ynet_kmeans2d`` (one workgroup per person; the reference
     loops over persons in Python); the first goal is the soft-argmax of the logits.  The initial centres are drawn
-    with np.random.choice per person, in order, like the reference.  -> [n_goal, B, 1, 2]."""
+    with np.random.choice per person, in order, like the reference.  -> [n_goal, B, 1, 2].
+    Status bit 0 (a cluster went empty) sends that person to the host path; status bit 1 (an initial-centre index outside
+    the point set) raises ValueError: the indices are drawn here, on the host, so that bit means a bug in this function."""
     if draw is None:
         draw = sampling(wp_sigmoid_last, num_samples=10000, replacement=True, rel_threshold=rel_thresh).permute(2, 0, 1, 3)
     first = model.softargmax(wp_logits_last)                     # [B,1,2]
@@ -419,7 +421,11 @@ def ttst_goals(model, wp_sigmoid_last, wp_logits_last, n_goal, rel_thresh, draw=
     points = draw[:, :, 0].permute(1, 0, 2).contiguous()         # [B, 10000, 2]
     init = torch.from_numpy(np.stack([np.random.choice(points.shape[1], k, replace=False) for _ in range(n_people)]).astype(np.int32))
     centers, status = ops.kmeans2d(points, init, tol=0.001, iter_limit=1000)
-    for person in torch.nonzero(status.cpu() & 1).flatten().tolist():
+    status = status.cpu()
+    if bool((status & 2).any()):
+        bad = torch.nonzero(status & 2).flatten().tolist()
+        raise ValueError(f"ttst_goals: kmeans2d was given an initial-centre index outside 0 .. {points.shape[1] - 1} for person(s) {bad}")
+    for person in torch.nonzero(status & 1).flatten().tolist():
         centers[person] = _kmeans_host_path(points[person], k, init[person])
     goals = centers.permute(1, 0, 2).unsqueeze(2)                # [k, B, 1, 2]
     return torch.cat([first.unsqueeze(0), goals], dim=0)

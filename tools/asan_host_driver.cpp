@@ -203,6 +203,8 @@ int main() {
     EXPECT_REJECT(ynet_heatmap_analytic(cfp, fp, 1, 4, 4, 8, 0, 0.0, nullptr, 0, &status, nullptr));
     EXPECT_REJECT(ynet_heatmap_analytic(cfp, fp, 1, 4, 4, 8, 1, 1.0, nullptr, 31, &status, nullptr));
     EXPECT_REJECT(ynet_kmeans2d(cfp, &one, fp, &status, 1, 20000, 4, 1e-3f, 10, nullptr));
+    EXPECT_REJECT(ynet_kmeans2d(cfp, &one, fp, &status, 1, 100, 4, 0.f, 0, nullptr));        // tol <= 0 without a limit: could not end
+    EXPECT_REJECT(ynet_kmeans2d(cfp, &one, fp, &status, 1, 100, 4, 1e-3f, -1, nullptr));
     EXPECT_REJECT(ynet_multinomial(cfp, 1, 4, 4, 99, 0, 0.f, 1ull, (long long*)dummy, &status, nullptr));
     EXPECT_REJECT(ynet_multinomial(cfp, 1, 4, 4, 1, 0, 2.f, 1ull, (long long*)dummy, &status, nullptr));
     EXPECT_REJECT(ynet_cws_prior(cfp, 4, 1, cfp, cfp, 1, 2, 2, 0.f, 1.f, 0, fp, fp, nullptr));
