@@ -598,6 +598,31 @@ int ynet_map_likelihood_sweep(const float* x, long long batch_stride, const floa
 int ynet_map_modes(const float* x, long long batch_stride, long long B, int C, int H, int W, int n_modes, int radius, float temperature,
                    float* xy, float* logit, float* mass, int* count, int* status, void* stream);
 
+/* Scene compliance of the goal map: the share of the distribution the goals are sampled from -- sigmoid(pred_goal_map / temperature),
+ * every plane normalised (utils/evaluate.py:128-131, utils/image_utils.py:110-135) -- that lies on each semantic class of the scene
+ * (the reference shows this as pictures only: evaluator/visualization.py plot_goal_output).  Per plane (b, c) of x [B][C][H][W] (batch
+ * stride `batch_stride` elements, so a channel slice needs no copy), with z = x / T, w = sigmoid(z) and Z = sum w over the whole plane:
+ *   mass [B][C][n_classes]:  mass[b][c][k] = (sum over {i : labels[i] == k} of w_i) / Z
+ * labels: one byte per pixel, [H][W].  label_batch_stride == 0: one label plane for the whole call; otherwise row b reads
+ * labels + b * label_batch_stride (bytes, >= H * W) and its C planes share it.  A label >= n_classes belongs to no class: its pixel
+ * counts in Z only and the row sums to less than 1 (documented behaviour, not an error).
+ * One workgroup per plane, one pass over x; w is fp32, formed exactly as ynet_map_likelihood forms it; sums, cross-wave combine and
+ * division are fp64, combined in a fixed order with no atomics: two runs give the same bits.  The class sums add the same four values
+ * in the same tree as Z (a pixel of another class enters as 0), so where every pixel of a plane has class k, mass[k] == 1.0f exactly,
+ * and a class that occurs nowhere has 0.0f exactly.  Planes that start on a 16-byte boundary, hold a multiple of 4 pixels and whose
+ * label plane starts on a 4-byte boundary are read in 16-byte vectors with one 4-byte label load each; any other plane element by
+ * element (decided per plane: nothing is assumed about alignment, a label pointer at any byte offset is legal).  Both paths add the
+ * same terms in the same order: a plane gives the same bits wherever it and its labels start.
+ * Rules: a NaN logit makes every class of its plane NaN; a -inf logit adds 0; +inf is weight 1; sigmoids below fp32's normal range
+ * count as 0; Z == 0 makes every class of its plane NaN.
+ * Refused (non-zero, ynet_last_error) before any launch: null x, labels or mass; n_classes outside 1 .. YNET_MAP_MAX_CLASSES;
+ * temperature <= 0 or not finite (or below 2.95e-39, where 1 / T is not); B, C, H or W < 1; H * W > 2^31 - 2048;
+ * batch_stride < C * H * W; label_batch_stride neither 0 nor >= H * W; B * C >= 2^31. */
+#define YNET_MAP_MAX_CLASSES 8
+int ynet_map_class_mass(const float* x, long long batch_stride, const unsigned char* labels, long long label_batch_stride,
+                        long long B, int C, int H, int W, int n_classes, float temperature, float* mass /* [B*C][n_classes] */,
+                        void* stream);
+
 /* ---- heat-map construction -------------------------------------------------------------------- */
 /* get_patch + torch.stack (utils/image_utils.py:40-63; utils/train_epoch.py:63-78;
  * utils/evaluate.py:112-114,250-253): out[n] = tmpl[SH/2 - ry : +H, SW/2 - rx : +W] with

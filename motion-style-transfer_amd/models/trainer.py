@@ -157,6 +157,22 @@ def apply_freeze_policy(model, train_net, position=(), network=None, ynet_bias=F
     return model
 
 
+def compliance_report(df_metrics, images):
+    """The lines test(return_compliance=True) prints per round, one per semantic class: the mean goal mass, the mean sampled-goal rate
+    and the share of ground-truth goals on the class (goals outside the map count in none), beside the share of the map the class
+    covers (agents weighted: every agent brings the areas of its own scene)."""
+    from ..utils.compliance import class_area, scene_labels
+    n_cls = sum(1 for c in df_metrics.columns if c.startswith("goal_mass_"))
+    area = {sid: class_area(scene_labels(images[sid]), n_cls).cpu().numpy() for sid in df_metrics["sceneId"].unique()}
+    mean_area = np.stack([area[sid] for sid in df_metrics["sceneId"]]).mean(axis=0)
+    gt = df_metrics["gt_goal_class"].to_numpy()
+    lines = ["Scene compliance (class: goal mass | sampled-goal rate | ground-truth goals | map area)"]
+    for k in range(n_cls):
+        lines.append(f"  class {k}: {df_metrics[f'goal_mass_{k}'].mean():.4f} | {df_metrics[f'sample_goal_rate_{k}'].mean():.4f} | "
+                     f"{float((gt == k).mean()):.4f} | {mean_area[k]:.4f}")
+    return "\n".join(lines)
+
+
 class YNetTrainer:
     def __init__(self, params, device=None):
         self.params = params
@@ -281,16 +297,19 @@ class YNetTrainer:
         return self.val_ADE, self.val_FDE
 
     # ------------------------------------------------------------------------------------------
-    def test(self, df_test, image_path, return_preds=False, return_samples=False, return_likelihood=False):
+    def test(self, df_test, image_path, return_preds=False, return_samples=False, return_likelihood=False, return_compliance=False):
         """``return_likelihood`` (not in the reference): evaluate() also scores the goal-map distribution against the ground truth
-        (df_metrics columns nll, nll_goal, entropy_goal, hpd_goal) and every round prints its mean NLL and calibration error."""
+        (df_metrics columns nll, nll_goal, entropy_goal, hpd_goal) and every round prints its mean NLL and calibration error.
+        ``return_compliance`` (not in the reference): evaluate() also reports where in the scene the goals go (df_metrics columns
+        goal_mass_<k>, gt_goal_class, sample_goal_rate_<k>) and every round prints one line per semantic class: the mean goal mass,
+        the mean sampled-goal rate and the share of ground-truth goals on the class, beside the share of the map the class covers."""
         return self._test(df_test, image_path, return_preds=return_preds, return_samples=return_samples,
-                          return_likelihood=return_likelihood, **self.params)
+                          return_likelihood=return_likelihood, return_compliance=return_compliance, **self.params)
 
     def _test(self, df_test, image_path, dataset_name, resize_factor, batch_size, n_round, obs_len, pred_len,
               waypoints, n_goal, n_traj, temperature, rel_threshold, use_TTST, use_CWS, CWS_params,
               use_raw_data=False, return_preds=False, return_samples=False, network=None, swap_semantic=False,
-              return_likelihood=False, **kwargs):
+              return_likelihood=False, return_compliance=False, **kwargs):
         test_images, test_loader, self.homo_mat = self.prepare_data(
             df_test, image_path, dataset_name, "test", obs_len, pred_len, resize_factor, use_raw_data)
         model = self.model.to(self.device)
@@ -304,7 +323,8 @@ class YNetTrainer:
                 model, test_loader, test_images, self.device, dataset_name, self.homo_mat, input_template, waypoints,
                 "test", n_goal, n_traj, obs_len, batch_size, resize_factor, temperature, use_TTST, use_CWS,
                 rel_threshold, CWS_params, return_preds=return_preds, return_samples=return_samples,
-                network=network, swap_semantic=swap_semantic, dp=self.dp, return_likelihood=return_likelihood)
+                network=network, swap_semantic=swap_semantic, dp=self.dp, return_likelihood=return_likelihood,
+                return_compliance=return_compliance)
             list_metrics.append(df_metrics)
             list_trajs.append(trajs_dict)
             print(f"Round {e}: \nTest ADE: {test_ADE} \nTest FDE: {test_FDE}")
@@ -313,6 +333,8 @@ class YNetTrainer:
                 hpd_goal = df_metrics["hpd_goal"].to_numpy()      # (all NaN when every goal lies outside its map: nothing to calibrate)
                 ece = calibration_curve(hpd_goal)[2] if np.isfinite(hpd_goal).any() else "n/a"
                 print(f"Test NLL: {df_metrics['nll'].mean()} \nTest goal ECE: {ece}")
+            if return_compliance:
+                print(compliance_report(df_metrics, test_images))
             self.eval_ADE.append(test_ADE)
             self.eval_FDE.append(test_FDE)
         avg_ade = sum(self.eval_ADE) / len(self.eval_ADE)

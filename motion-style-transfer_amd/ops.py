@@ -2901,6 +2901,42 @@ def check_likelihood_status(raise_error: bool = True) -> bool:
     return hit
 
 
+MAP_MAX_CLASSES = 8      # YNET_MAP_MAX_CLASSES of include/ynet_hip.h
+
+
+def map_class_mass(x: torch.Tensor, labels: torch.Tensor, n_classes: int, temperature: float = 1.0) -> torch.Tensor:
+    """Scene compliance of the distribution `sampling` draws from (ynet_map_class_mass; utils/evaluate.py:128-131,
+    utils/image_utils.py:110-135): per plane of x [B, C, H, W], p = sigmoid(x / T) normalised to sum 1, in one pass over x;
+    -> [B, C, n_classes] float32 device tensor, entry k = the share of p on the pixels whose label is k.
+    ``labels``: uint8 device tensor, one class per pixel, [H, W] (one scene for the whole batch) or [B, H, W] (one per row, shared
+    by the row's C planes); its last two dimensions must be contiguous, a view starting at any byte offset is legal.  A label
+    >= n_classes belongs to no class: its pixel counts in the normalisation only, and the row sums to less than 1.
+    1 <= n_classes <= 8.  A channel view such as x[:, -1:] is read in place.  Not differentiable.  A plane that holds a NaN logit, or
+    whose weights are all 0, gives NaN for every class."""
+    t, c, bs = _plane_desc(x.detach() if torch.is_tensor(x) else x, "map_class_mass")
+    B, _, H, W = t.shape
+    K = int(n_classes)
+    if not 1 <= K <= MAP_MAX_CLASSES:
+        raise ValueError(f"map_class_mass: n_classes = {K}, expected 1 .. {MAP_MAX_CLASSES}")
+    if not (float(temperature) > 0 and np.isfinite(float(temperature))):
+        raise ValueError(f"map_class_mass: temperature {temperature!r} must be positive and finite")
+    _need_gpu(labels, "map_class_mass labels", dtypes=(torch.uint8,))
+    if tuple(labels.shape) not in ((H, W), (B, H, W)):
+        raise ValueError(f"map_class_mass: labels {tuple(labels.shape)} do not go with the map {tuple(t.shape)} (expected {(H, W)} or {(B, H, W)})")
+    ls = labels.stride()
+    if not ((W == 1 or ls[-1] == 1) and (H == 1 or ls[-2] == W)):
+        raise ValueError(f"map_class_mass: the label planes must be contiguous (strides {tuple(ls)} for {tuple(labels.shape)})")
+    lbs = 0
+    if labels.dim() == 3 and B > 1:
+        lbs = ls[0]
+        if lbs != 0 and lbs < H * W:      # (0: an expanded view, one plane for every row)
+            raise ValueError(f"map_class_mass: label batch stride {lbs} below the {H}x{W} bytes of a plane")
+    out = torch.empty((B, c, K), device=t.device, dtype=torch.float32)
+    lib = _lib()
+    L.check(lib.ynet_map_class_mass(t.data_ptr(), bs, labels.data_ptr(), lbs, B, c, H, W, K, float(temperature), out.data_ptr(), _stream()), lib)
+    return out
+
+
 _modes_status = {}
 MAX_MODES = 64      # ynet_map_modes takes up to the MAX_SAMPLES of the ranking kernel
 

@@ -209,7 +209,7 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
              n_goal, n_traj, obs_len, batch_size, resize_factor=0.25, temperature=1, use_TTST=False, use_CWS=False,
              rel_thresh=0.002, CWS_params=None, return_preds=False, return_samples=False, network=None,
              swap_semantic=False, forced_samples=None, dp=None, max_effective_batch=256, forced_goals=None,
-             forced_ttst_samples=None, return_likelihood=False):
+             forced_ttst_samples=None, return_compliance=False, return_likelihood=False):
     """utils/evaluate.py:37-315.  Extra keyword arguments (tests / data-parallel runs): ``forced_samples`` [K,B,nwp,2]
     per batch replaces every random draw, ``forced_goals`` [n_goal,B,1,2] per batch only the goal draw,
     ``forced_ttst_samples`` [10000,B,1,2] per batch the TTST draw; ``dp`` shards each batch over ranks.
@@ -218,7 +218,14 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
     columns ``nll`` (mean over the pred_len steps, nats), ``nll_goal``, ``entropy_goal`` and ``hpd_goal`` (last step), and with
     ``return_preds`` trajs_dict gains ``nll_steps``, ``entropy_steps`` and ``hpd_steps`` [N, pred_len].  A step whose ground truth
     lies outside the map has NaN nll / hpd (one warning per call).  The sweep then takes the
-    branch ``return_preds`` takes (same launches and draws otherwise; the captured sweep is neither used nor touched)."""
+    branch ``return_preds`` takes (same launches and draws otherwise; the captured sweep is neither used nor touched).
+    ``return_compliance`` connects that distribution to the scene (ops.map_class_mass).  The classes are
+    utils.compliance.scene_labels(val_images[scene_id]) -- the world's classes, taken before ``swap_semantic`` and the scene
+    embedding, K = the number of planes (a scene with more than 8 raises before the sweep starts).  df_out gains ``goal_mass_<k>``
+    (the share of the last step's distribution on class k), ``gt_goal_class`` (the class of the ground-truth goal pixel, -1
+    outside the map) and ``sample_goal_rate_<k>`` (the fraction of the sampled goals on class k); with ``return_preds``
+    trajs_dict gains ``class_mass_steps`` [N, pred_len, K].  One launch per batch; the sweep takes the branch ``return_preds``
+    takes, as for ``return_likelihood``."""
     model.eval()
     waypoints = list(waypoints)
     n_wp = len(waypoints)
@@ -231,6 +238,14 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
         trajs_dict = None
     like_lists = {k: [] for k in ops.LIKELIHOOD_OUTPUTS} if return_likelihood else None
     like_warned = False
+    comp_lists = {k: [] for k in ("mass", "gt_class", "rate")} if return_compliance else None
+    scene_label_maps = {}      # scene id -> (labels [H, W] uint8 on the device, K)
+    if return_compliance:
+        from .compliance import MAX_CLASSES, point_classes, class_rates, scene_labels
+        for sid, im in val_images.items():      # (before the sweep starts, not at the first batch of the offending scene)
+            if im.dim() == 3 and im.shape[0] > MAX_CLASSES:
+                raise ValueError(f"evaluate(return_compliance=True): scene {sid} has {im.shape[0]} planes; the classes of at most "
+                                 f"{MAX_CLASSES} planes are told apart")
 
     with torch.no_grad():
         # Every packed filter is (re)written HERE, on the caller's stream: the K-sample passes below run the trajectory decoder on two
@@ -241,7 +256,7 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
         if return_likelihood:
             ops.check_likelihood_status()      # a report left pending by an earlier ops.map_likelihood call of the caller's is raised, not swallowed below
         plain = (forced_samples is None and forced_goals is None and not use_TTST and not use_CWS and not return_preds
-                 and not return_samples and dataset_name != "eth" and not return_likelihood)
+                 and not return_samples and dataset_name != "eth" and not return_likelihood and not return_compliance)
         sa = getattr(model, "softargmax_", None)
         hooked = sa is not None and (sa._forward_hooks or sa._forward_pre_hooks)
         graphs = None
@@ -254,6 +269,8 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
         try:
             for trajectory, df_batch, scene_id in val_loader:
                 scene_image = model.segmentation(val_images[scene_id].to(device).unsqueeze(0))
+                if return_compliance and scene_id not in scene_label_maps:      # once per scene, from the planes as prepare_data left them
+                    scene_label_maps[scene_id] = (scene_labels(val_images[scene_id].to(device)), val_images[scene_id].shape[0])
                 scene_image = model.adapt_semantic(scene_image)
                 meta_ids = df_batch[0].metaId.unique()
                 n_data = trajectory.shape[0]
@@ -310,6 +327,10 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                                                                          input_template, waypoints, obs_len, temperature, network)
                         if return_likelihood:      # every step's plane against its ground truth, in resized pixels: one launch
                             like = ops.map_likelihood(pred_goal_map, gt_future, temperature)
+                        if return_compliance:      # every step's plane against the scene's label map: one launch
+                            labels, n_cls = scene_label_maps[scene_id]
+                            comp = {"mass": ops.map_class_mass(pred_goal_map, labels, n_cls, temperature),
+                                    "gt_class": point_classes(gt_future[:, -1], labels)}
 
                         if forced_samples is not None:
                             waypoint_samples = forced_samples[b][:, lo:lo + n_local].to(device)
@@ -320,6 +341,8 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                                                                use_TTST, use_CWS, rel_thresh, CWS_params, mine(forced_goals),
                                                                mine(forced_ttst_samples))
 
+                        if return_compliance:      # the goals as drawn, in the map's pixels (before ETH's world coordinates)
+                            comp["rate"] = class_rates(point_classes(waypoint_samples[:, :, -1], labels), n_cls, dim=0).t().contiguous()
                         if return_samples:
                             trajs_dict["goal_map"].append(pred_goal_map.cpu().numpy())
                             trajs_dict["goal_sigmoid_map"].append(model.sigmoid(pred_goal_map / temperature).cpu().numpy())
@@ -342,13 +365,23 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                         ade = fde = torch.zeros(0, device=device)
                         if return_likelihood:
                             like = {k: torch.zeros((0, trajectory.shape[1] - obs_len), device=device) for k in ops.LIKELIHOOD_OUTPUTS}
+                        if return_compliance:
+                            n_cls = scene_label_maps[scene_id][1]
+                            comp = {"mass": torch.zeros((0, trajectory.shape[1] - obs_len, n_cls), device=device),
+                                    "gt_class": torch.zeros(0, device=device, dtype=torch.int64),
+                                    "rate": torch.zeros((0, n_cls), device=device, dtype=torch.float64)}
                     if dp is not None:
                         sizes = dp.shard_sizes(n_global)
                         ade, fde = dp.gather_rows(ade, sizes), dp.gather_rows(fde, sizes)
                         if return_likelihood:
                             like = {k: dp.gather_rows(v, sizes) for k, v in like.items()}
+                        if return_compliance:
+                            comp = {k: dp.gather_rows(v, sizes) for k, v in comp.items()}
                     ade_list.append(ade.cpu().numpy())
                     fde_list.append(fde.cpu().numpy())
+                    if return_compliance:
+                        for k, v in comp.items():
+                            comp_lists[k].append(v.cpu().numpy())
                     if return_likelihood:
                         for k, v in like.items():
                             like_lists[k].append(v.cpu().numpy())
@@ -373,9 +406,23 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
         df_out["nll_goal"] = steps["nll"][:, -1]
         df_out["entropy_goal"] = steps["entropy"][:, -1]
         df_out["hpd_goal"] = steps["hpd"][:, -1]
+    if return_compliance:
+        widths = {m.shape[-1] for m in comp_lists["mass"]}
+        if len(widths) != 1:
+            raise ValueError(f"evaluate(return_compliance=True): the scenes differ in their number of planes ({sorted(widths)}); "
+                             f"one table needs one set of classes")
+        mass_steps = np.concatenate(comp_lists["mass"], axis=0)      # [N, pred_len, K]
+        rates = np.concatenate(comp_lists["rate"], axis=0)
+        for k in range(mass_steps.shape[-1]):
+            df_out[f"goal_mass_{k}"] = mass_steps[:, -1, k]
+        df_out["gt_goal_class"] = np.concatenate(comp_lists["gt_class"], axis=0)
+        for k in range(rates.shape[-1]):
+            df_out[f"sample_goal_rate_{k}"] = rates[:, k]
     if return_preds:
         for key, value in trajs_dict.items():
             trajs_dict[key] = np.concatenate(value, axis=0)
+        if return_compliance:
+            trajs_dict["class_mass_steps"] = mass_steps
         if return_likelihood:
             for k, v in steps.items():
                 trajs_dict[k + "_steps"] = v

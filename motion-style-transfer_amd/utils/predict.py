@@ -15,6 +15,9 @@ models.style_bank.StyleBank, one call.
 
 ``predict_modes`` is predict() with no draw at all: the goals are the modes of the goal map's logits under greedy non-maximum
 suppression (ops.map_modes), each with the probability mass it claims.
+
+``predict_with_entropy`` and ``predict_with_compliance`` are predict() plus one read-out of the goal map each: its entropy
+(DESIGN.md section 4.10), and the share of it on every semantic class of the scene (ops.map_class_mass).
 """
 import functools
 import inspect
@@ -109,10 +112,12 @@ def _mode_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, n_modes,
 
 def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
               use_TTST, use_CWS, rel_thresh, CWS_params, network, swap_semantic, batch_size, max_effective_batch, forced_samples, return_maps,
-              return_entropy, modes=None):
+              return_entropy, modes=None, return_compliance=False):
     """The one body of predict(), predict_with_entropy(), predict_styles() and predict_modes(), on arguments that went through _validated.
     modes              None, or (n_modes, radius): the way-points are not drawn but read off the goal map (_mode_waypoints; then
                        n_goal = n_modes, n_traj = 1, and the results gain ``mode_mass`` and ``mode_logit``)
+    return_compliance  the results gain ``goal_class_mass`` [N, pred_len, K]: one ops.map_class_mass launch per chunk against
+                       utils.compliance.scene_labels(scene_image), the classes of the scene as given (before ``swap_semantic``)
     refresh()          packs the filters the chunks will read, on the caller's stream, before the decoder passes fan out over two (see
                        evaluate()): ops.refresh_filters(model), or a StyleBank's refresh() for its shadows and the shared layers
     chunk_plan(b, n)   for the n agents from b on -> (perm, pred_features): ``perm`` None, or the order the chunk runs in (row j of the
@@ -127,11 +132,15 @@ def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template
     was_training = model.training
     model.eval()
     out = {k: [] for k in ["trajectories", "waypoints", "scores", "order"] + (["goal_map", "goal_sigmoid_map"] if return_maps else [])
-           + (["entropy"] if return_entropy else []) + (["mode_mass", "mode_logit"] if modes is not None else [])}
+           + (["entropy"] if return_entropy else []) + (["mode_mass", "mode_logit"] if modes is not None else [])
+           + (["goal_class_mass"] if return_compliance else [])}
     try:
         with torch.no_grad():
             refresh()
             scene = model.segmentation(scene_image.to(device).unsqueeze(0))
+            if return_compliance:
+                from .compliance import scene_labels
+                labels = scene_labels(scene_image.to(device))      # (more than 8 planes: refused here, before any chunk runs)
             scene = model.adapt_semantic(scene)
             if swap_semantic:
                 scene = swap_pavement_terrain(scene)
@@ -176,6 +185,8 @@ def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template
                         out[k].append(v)
                 if return_entropy:
                     out["entropy"].append(ops.map_likelihood(pred_goal_map, None, temperature, want=("entropy",))["entropy"])
+                if return_compliance:
+                    out["goal_class_mass"].append(ops.map_class_mass(pred_goal_map, labels, scene_image.shape[0], temperature))
 
                 trajs_samples = _decoder_passes(model, features, waypoint_samples, input_template, n, n_wp, H, W, max_effective_batch, device)
                 ranking = (wp_sigmoid, waypoint_samples, trajs_samples.contiguous(), resize_factor)
@@ -215,7 +226,8 @@ def predict(model, scene_image, observed, input_template, waypoints, n_goal, n_t
        trajs_dict["prediction"]), ``waypoints`` [N, K, n_wp, 2] (resized pixels, as sampled), ``scores`` [N, K] descending,
        ``order`` [N, K] int32 (row r is sample order[:, r] of the sweep), and with ``return_maps`` ``goal_map`` [N, pred_len, H, W]
        and ``goal_sigmoid_map`` as evaluate(return_samples=True) stores them.
-       predict_with_entropy() is this call plus ``entropy`` [N, pred_len]: how spread out every step's goal-map distribution is."""
+       predict_with_entropy() is this call plus ``entropy`` [N, pred_len]: how spread out every step's goal-map distribution is;
+       predict_with_compliance() is this call plus ``goal_class_mass`` [N, pred_len, K]: the share of it on every class of the scene."""
     return _predict(False, **locals())
 
 
@@ -228,6 +240,21 @@ def predict_with_entropy(*args, **kwargs):
     bound = _PREDICT_SIGNATURE.bind(*args, **kwargs)
     bound.apply_defaults()
     return _predict(True, **bound.arguments)
+
+
+def predict_with_compliance(*args, return_entropy=False, **kwargs):
+    """predict() with the same arguments, and one more result: ``goal_class_mass`` [N, pred_len, K] (device tensor, float32), the share
+    of every future step's goal-map distribution -- sigmoid(pred_goal_map / T) normalised per plane, what `sampling` draws from -- that
+    lies on each of the K classes of the scene (ops.map_class_mass, one launch per chunk).  The classes are
+    utils.compliance.scene_labels(scene_image): K = the planes of ``scene_image`` (at most 8), taken as given, before
+    ``swap_semantic``.  The values are the ones evaluate(return_compliance=True) reports as ``class_mass_steps``.
+    ``return_entropy=True`` (keyword only) adds predict_with_entropy()'s ``entropy`` as well.  Every other result is predict()'s, bit
+    for bit: no draw is added or moved.
+    (A function of its own and not a keyword of predict(), as predict_with_entropy(): predict()'s parameter list is pinned by
+    tests/test_predict_host.py, and predict_styles mirrors it.)"""
+    bound = _PREDICT_SIGNATURE.bind(*args, **kwargs)
+    bound.apply_defaults()
+    return _predict(bool(return_entropy), **bound.arguments, return_compliance=True)
 
 
 def _predict(return_entropy, model, scene_image, observed, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
@@ -255,6 +282,7 @@ def predict_styles(bank, scene_image, observed, style, input_template, waypoints
     forced_samples   as for predict(), in the CALLER's order: {first agent of a chunk: [K, n, n_wp, 2]} or one tensor [K, N, n_wp, 2]
     every other argument and every result as for predict(); the results are in the caller's order and carry ``style_index`` [N] (int64).
     The goal-map entropy of predict_with_entropy() is out of scope here for now: there is no predict_styles form of it.
+    Neither is the scene compliance of predict_with_compliance(): out of scope here for now.
 
     Each chunk (``batch_size`` agents of the caller's order; it may hold any subset of the styles) is stable-sorted by style index on
     the host -- the labels are host data.  ynet_gather_rows builds the sorted observed coordinates and forced samples, and
@@ -296,8 +324,8 @@ def predict_modes(model, scene_image, observed, input_template, waypoints, n_mod
        order[:, r]): the share of sigmoid(goal_map / T), normalised, that the mode claimed -- the masses of an agent are disjoint and
        sum to the covered share of its map -- and the raw logit of its peak.  With one way-point ``order`` is 0 .. n_modes - 1.
     An agent whose goal map gives fewer modes (non-finite logits) raises RuntimeError at the chunk's sync point.
-    Out of scope for now: a predict_styles form, evaluate() over modes, sub-pixel refinement of the peak, and capturing the call into
-    a hipGraph."""
+    Out of scope for now: a predict_styles form, evaluate() over modes, sub-pixel refinement of the peak, capturing the call into
+    a hipGraph, and the scene compliance of predict_with_compliance() (the class mass of the goal map)."""
     n_modes, radius = int(n_modes), int(radius)
     if not 1 <= n_modes <= MAX_SAMPLES:
         raise ValueError(f"predict_modes: n_modes = {n_modes}; the ranking kernel takes 1 .. {MAX_SAMPLES}")

@@ -227,6 +227,23 @@ int main() {
     EXPECT_REJECT(ynet_map_likelihood(cfp, 16, nullptr, 1, 1, 4, 4, 1.f, fp, fp, nullptr, &status, nullptr));            // nll without the ground truth
     EXPECT_REJECT(ynet_map_likelihood(cfp, 16, nullptr, 1, 1, 4, 4, 1.f, nullptr, fp, fp, &status, nullptr));            // hpd without the ground truth
     EXPECT_REJECT(ynet_map_likelihood(cfp, 16, cfp, 1, 1, 4, 4, 1.f, fp, fp, fp, nullptr, nullptr));                     // ground truth without a status flag
+    {
+        const unsigned char* lab = reinterpret_cast<const unsigned char*>(dummy);
+        EXPECT_REJECT(ynet_map_class_mass(nullptr, 16, lab, 0, 1, 1, 4, 4, 6, 1.f, fp, nullptr));                        // no map
+        EXPECT_REJECT(ynet_map_class_mass(cfp, 16, nullptr, 0, 1, 1, 4, 4, 6, 1.f, fp, nullptr));                        // no labels
+        EXPECT_REJECT(ynet_map_class_mass(cfp, 16, lab, 0, 1, 1, 4, 4, 6, 1.f, nullptr, nullptr));                       // no output
+        EXPECT_REJECT(ynet_map_class_mass(cfp, 16, lab, 0, 1, 1, 4, 4, 0, 1.f, fp, nullptr));                            // n_classes outside 1 .. 8
+        EXPECT_REJECT(ynet_map_class_mass(cfp, 16, lab, 0, 1, 1, 4, 4, YNET_MAP_MAX_CLASSES + 1, 1.f, fp, nullptr));
+        EXPECT_REJECT(ynet_map_class_mass(cfp, 16, lab, 0, 1, 1, 4, 4, 6, 0.f, fp, nullptr));                            // temperature 0
+        EXPECT_REJECT(ynet_map_class_mass(cfp, 16, lab, 0, 1, 1, 4, 4, 6, 0.f / 0.f, fp, nullptr));                      // not finite
+        EXPECT_REJECT(ynet_map_class_mass(cfp, 16, lab, 0, 1, 1, 4, 4, 6, 1e-39f, fp, nullptr));                         // a denormal: 1 / T overflows
+        EXPECT_REJECT(ynet_map_class_mass(cfp, 1ll << 31, lab, 0, 1, 1, 32768, 65536, 6, 1.f, fp, nullptr));             // 2^31 pixels per plane
+        EXPECT_REJECT(ynet_map_class_mass(cfp, 16, lab, 0, 0, 1, 4, 4, 6, 1.f, fp, nullptr));                            // B, C, H, W < 1
+        EXPECT_REJECT(ynet_map_class_mass(cfp, 16, lab, 0, 1, 1, 4, 0, 6, 1.f, fp, nullptr));
+        EXPECT_REJECT(ynet_map_class_mass(cfp, 31, lab, 0, 2, 2, 4, 4, 6, 1.f, fp, nullptr));                            // batch stride below the image
+        EXPECT_REJECT(ynet_map_class_mass(cfp, 32, lab, 15, 2, 2, 4, 4, 6, 1.f, fp, nullptr));                           // label stride neither 0 nor a plane
+        EXPECT_REJECT(ynet_map_class_mass(cfp, 4, lab, 0, 1ll << 29, 4, 1, 1, 6, 1.f, fp, nullptr));                     // 2^31 planes
+    }
     {   // the sweep reads its temperatures on the host: exactly n_temps of them (a heap array of that length, so a read past it is seen)
         float* t32 = new float[YNET_SWEEP_MAX_TEMPS];
         float* t3 = new float[3];
