@@ -406,7 +406,9 @@ int ynet_lora_compose_pack_multi(int n, const float* const* w, const float* cons
  * computed from 9 r planes projected out of x (through lora_A) and out of dy (through lora_B): (54 cin + 18 cout) r MACs
  * per pixel instead of 9 cin cout, no dW round trip through HBM.  `mask`: the conv's post-ReLU output (dy is zeroed where
  * it is <= 0) or NULL.  Sources: the virtual concatenation of the conv's inputs, as for ynet_conv2d_wgrad; 16-byte aligned
- * planes, W % 4 == 0.  workspace: ynet_lora_conv2d_wgrad_workspace_floats(cin, cout) floats.
+ * planes, W % 4 == 0; one image of a source (src_c * H * W floats) must span fewer than 2^31 bytes -- the kernel addresses it by
+ * 32-bit byte offsets -- and a larger one is refused before any launch.  workspace: ynet_lora_conv2d_wgrad_workspace_floats(cin,
+ * cout) floats (1024 slabs of partial sums; the persistent grid never has more workgroups than that).
  * ynet_lora_conv2d_wgrad_supported: K == 3, r == 1, cin, cout <= 64, W % 4 == 0 (anything else: the two-call chain). */
 int ynet_lora_conv2d_wgrad_supported(int cin, int cout, int K, int r, int W);
 /* ... and where it is also the faster of the two paths (the layers with more than 32 output channels; measured) */

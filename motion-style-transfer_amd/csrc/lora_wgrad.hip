@@ -32,6 +32,7 @@
 
 #define LW_RQ 3              // r * K rows of lora_A / columns of lora_B (r = 1, K = 3)
 #define LW_ROWS 9            // projected planes: (ii, q)
+#define LW_MAX_WG 1024       // slabs of partial sums in the workspace = the largest grid
 
 struct LoraWgArgs {
     YSrc src[YNET_MAX_SRC];   // x = virtual concat of the sources
@@ -504,7 +505,8 @@ static int lw_grid(int ntiles, int lds_bytes) {
     static const int cap = getenv("YNET_LW_WG_PER_CU") ? atoi(getenv("YNET_LW_WG_PER_CU")) : 3;
     if (per_cu > cap) per_cu = cap;
     if (per_cu < 1) per_cu = 1;
-    const int slots = per_cu * cus;
+    int slots = per_cu * cus;
+    if (slots > LW_MAX_WG) slots = LW_MAX_WG;      // (a raised YNET_LW_WG_PER_CU: never more workgroups than the workspace has slabs)
     return ntiles < slots ? ntiles : slots;
 }
 
@@ -559,7 +561,7 @@ int ynet_lora_conv2d_wgrad_preferred(int cin, int cout, int K, int r, int W) {
 }
 
 long long ynet_lora_conv2d_wgrad_workspace_floats(int cin, int cout) {
-    return 1024ll * LW_ROWS * (9ll * cin + cout);       // one slab per resident workgroup (2 per CU, <= 512 CUs)
+    return (long long)LW_MAX_WG * LW_ROWS * (9ll * cin + cout);       // one slab per workgroup of the persistent grid (lw_grid: at most LW_MAX_WG)
 }
 
 int ynet_lora_conv2d_wgrad(const float* const* src, const int* src_c, const long long* src_bs, int nsrc,
@@ -576,6 +578,8 @@ int ynet_lora_conv2d_wgrad(const float* const* src, const int* src_c, const long
     for (int i = 0; i < nsrc; ++i) {
         YNET_REQUIRE(src[i] != nullptr && src_c[i] > 0, "lora_conv2d_wgrad: source %d is null/empty", i);
         YNET_REQUIRE(!misaligned(src[i], src_bs[i]), "lora_conv2d_wgrad: source %d is not 16-byte aligned", i);
+        // the x-tile DMA addresses one image of a source by 32-bit byte offsets, 0x80000000 marks "outside the image"
+        YNET_REQUIRE((long long)src_c[i] * H * W * 4 < (1ll << 31), "lora_conv2d_wgrad: source %d spans 2^31 bytes or more per image (%d channels of %d x %d)", i, src_c[i], H, W);
         a.src[i] = YSrc{src[i], src_c[i], src_bs[i], 0};
         a.cin += src_c[i];
     }

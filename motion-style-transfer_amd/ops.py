@@ -282,9 +282,11 @@ def lora_compose_pack(w, lora_a, lora_b, scale: float, bufs=None):
 def lora_grad(dw, lora_a, lora_b, scale: float):
     cout, cin, k, _ = dw.shape
     r = lora_a.shape[0] // k
-    d_a, d_b = torch.empty_like(lora_a), torch.empty_like(lora_b)
+    # the kernel reads and writes row-major: contiguous operands first, outputs shaped like THOSE (empty_like of a transposed view keeps its strides)
+    dw, la, lb = dw.contiguous(), lora_a.contiguous(), lora_b.contiguous()
+    d_a, d_b = torch.empty_like(la), torch.empty_like(lb)
     lib = _lib()
-    L.check(lib.ynet_lora_grad(dw.data_ptr(), lora_a.contiguous().data_ptr(), lora_b.contiguous().data_ptr(), scale,
+    L.check(lib.ynet_lora_grad(dw.data_ptr(), la.data_ptr(), lb.data_ptr(), scale,
                                d_a.data_ptr(), d_b.data_ptr(), cout, cin, k, r, _stream()), lib)
     return d_a, d_b
 

@@ -168,6 +168,7 @@ int main() {
     EXPECT_REJECT(ynet_lora_conv2d_wgrad(srcs, &one, &bs, 1, nullptr, 4, nullptr, 0, cfp, cfp, 1.f, fp, fp, fp, 1, 4, 4, 4, 3, 1, nullptr));   // no dy
     EXPECT_REJECT(ynet_lora_conv2d_wgrad(srcs, &one, &bs, 1, cfp, 4, nullptr, 0, cfp, cfp, 1.f, fp, fp, fp, 1, 4, 4, 4, 3, 4, nullptr));       // rank 4
     EXPECT_REJECT(ynet_lora_conv2d_wgrad(srcs, &one, &bs, 1, cfp, 4, nullptr, 0, cfp, cfp, 1.f, fp, fp, fp, 1, 4, 6, 4, 3, 1, nullptr));       // W % 4
+    EXPECT_REJECT(ynet_lora_conv2d_wgrad(srcs, &one, &bs, 1, cfp, 4, nullptr, 0, cfp, cfp, 1.f, fp, fp, fp, 1, 32768, 16384, 4, 3, 1, nullptr)); // 2^31 bytes per source image
     EXPECT_REJECT(ynet_lora_compose_pack_multi(0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
     EXPECT_REJECT(ynet_lora_compose_pack_multi(99, srcs, srcs, srcs, cfp, dsts, dsts, &one, &one, &one, &one, nullptr));
     EXPECT_REJECT(ynet_adam_step(nullptr, &one, (const long long*)dummy, 1, 1, 1e-3, 0.9, 0.999, 1e-8, 0.0, 0, nullptr));     // no table
