@@ -56,7 +56,7 @@ int ynet_pack_weight(const float* w, float* wp, int cout, int cin, int K, int mo
  *   lets small-map launches (8^2 .. 32^2) split their input-channel loop over more workgroups.
  * Alignment: ynet_conv2d and ynet_conv2d_wgrad serve sources, mask, dy and destinations at ANY 4-byte address and any batch
  *   stride; the LDS-DMA / streaming kernels need every plane on a 16-byte boundary (pointer % 16 == 0, batch stride % 4 == 0,
- *   W % 4 == 0), anything else takes the register-staged tiles (same results within rounding, slower).  The epilogue variants
+ *   W % 4 == 0 -- for the 1x1 streaming filter gradient H * W % 16 == 0 instead), anything else takes the register-staged tiles (same results within rounding, slower).  The epilogue variants
  *   below exist in the LDS-DMA kernels only: ynet_conv2d_pool, ynet_conv2d_add, ynet_conv2d_relu_bits and
  *   ynet_conv2d_dgrad_relu_bits REFUSE a source, mask, destination or addend off that boundary, and ynet_conv2d_dgrad_relu a
  *   relu_of off it, before anything is launched (the message names the operand).  INTEGRATION.md has the table.
@@ -375,6 +375,22 @@ int ynet_conv2d_wgrad(const float* const* src, const int* src_c, const long long
                       const float* dy, long long dy_bs, const float* mask, long long mask_bs,
                       float* dw, float* db, float* workspace, int B, int H, int W, int cout, int K,
                       void* stream);
+/* What ynet_conv2d_wgrad WOULD launch for this problem, without launching anything (host code only, as ynet_conv2d_auto_plan): the same function
+ * plans the call itself, under the same YNET_WGRAD_* overrides.  masked: a mask operand is given; aligned: every plane the call is given -- each source,
+ * dy, the mask -- lies on a 16-byte boundary with a batch stride % 4 == 0 (what the call reads from its pointers); want_bias: db != NULL.
+ * partial_floats <= ynet_conv2d_wgrad_workspace_floats(B, H, W, cout, sum(src_c), K) for every problem.  Returns non-zero (ynet_last_error) for
+ * arguments ynet_conv2d_wgrad refuses. */
+typedef struct YnetWgradPlan {
+    int kernel;        /* the code ynet_conv2d_last_launch(1) reports: 1 staged, 2 LDS-DMA two-row tiles, 3 rolling rows, 4 1x1 streaming */
+    int rows;          /* rows per tile (4 staged, 2 DMA / rolling; 0 for streaming) */
+    int tiles_x, tiles_y, ntiles, co_blks, ci_blks;
+    int nsplit;        /* workgroups per channel block = partial slices the reduce sums (streaming: its grid) */
+    int seg, nseg_y, nsegs;                /* rolling rows only, else 0 */
+    int ct;            /* streaming only: 1 or 2 output-channel tiles */
+    long long partial_floats;              /* floats of workspace the launch writes, bias partials included when want_bias */
+} YnetWgradPlan;
+int ynet_conv2d_wgrad_plan(int B, int H, int W, int cout, const int* src_c, int nsrc, int K,
+                           int masked, int aligned, int want_bias, YnetWgradPlan* out);
 
 /* ---- MoSA / LoRA (loralib==0.1.1 Conv2d, call site models/ynet.py:141-144) -------------------
  * lora_a [r*K][cin*K], lora_b [cout*K][r*K], scale = lora_alpha / r (lora_alpha = 1).

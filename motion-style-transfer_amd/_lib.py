@@ -38,6 +38,12 @@ class ConvTaken(ctypes.Structure):
                 ("transformed", c_i), ("wrote_s2d", c_i)]
 
 
+class WgradPlan(ctypes.Structure):
+    """YnetWgradPlan: what ynet_conv2d_wgrad would launch (ynet_conv2d_wgrad_plan)."""
+    _fields_ = [("kernel", c_i), ("rows", c_i), ("tiles_x", c_i), ("tiles_y", c_i), ("ntiles", c_i), ("co_blks", c_i), ("ci_blks", c_i),
+                ("nsplit", c_i), ("seg", c_i), ("nseg_y", c_i), ("nsegs", c_i), ("ct", c_i), ("partial_floats", c_ll)]
+
+
 AUTO_NO_WINOGRAD, AUTO_NO_WINOGRAD16, AUTO_WINOGRAD16_FOR_16, AUTO_NO_POOL_CODE, AUTO_NO_RELU_WBITS, AUTO_NO_SPLIT48 = 1, 2, 4, 8, 16, 32
 AUTO_UPCONV_BWD = 64      # the form of ynet_conv2d_auto that runs an up-convolution's data gradient at the low resolution (wp = the raw filter)
 
@@ -100,6 +106,7 @@ SIGNATURES = {
     "ynet_conv2d_wgrad_workspace_floats": (c_ll, [c_i, c_i, c_i, c_i, c_i, c_i]),
     "ynet_conv2d_wgrad": (c_i, [PP, PI, PLL, c_i, c_fp, c_ll, c_fp, c_ll, c_fp, c_fp, c_fp,
                                 c_i, c_i, c_i, c_i, c_i, c_fp]),
+    "ynet_conv2d_wgrad_plan": (c_i, [c_i, c_i, c_i, c_i, PI, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(WgradPlan)]),
     "ynet_lora_compose": (c_i, [c_fp, c_fp, c_fp, c_f, c_fp, c_i, c_i, c_i, c_i, c_fp]),
     "ynet_lora_grad": (c_i, [c_fp, c_fp, c_fp, c_f, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp]),
     "ynet_lora_conv2d_wgrad_supported": (c_i, [c_i, c_i, c_i, c_i, c_i]),

@@ -19,6 +19,7 @@
 // Both split the pixels over `nsplit` workgroups and reduce the partials with reduce_partials_kernel in a fixed
 // order: bitwise reproducible, no float atomics.
 #include "ynet_common.h"
+#include "../../include/ynet_hip.h"
 #include <type_traits>
 #include <stdlib.h>
 #include <stdio.h>
@@ -1274,15 +1275,8 @@ static int launch_wgrad_dma(WgradArgs& a, float* dw, float* db, hipStream_t st) 
     return ynet_check_launch("conv2d_wgrad(reduce)");
 }
 
-// 1x1, one 32-channel source, <= 32 output channels, no mask, whole 16-pixel chunks, 16-byte aligned planes
-static const int WG1X1_BLOCKS = 512;
-static bool wgrad1x1_stream_ok(const WgradArgs& a, int K) {
-    static const int on = getenv("YNET_WGRAD_1X1_STREAM") ? atoi(getenv("YNET_WGRAD_1X1_STREAM")) : 1;
-    return on && K == 1 && a.nsrc == 1 && a.cin == 32 && a.cout <= 32 && a.mask == nullptr && ((long long)a.H * a.W) % 16 == 0 &&
-           (reinterpret_cast<uintptr_t>(a.src[0].p) & 15) == 0 && (a.src[0].bs & 3) == 0 && (reinterpret_cast<uintptr_t>(a.dy) & 15) == 0 && (a.dy_bs & 3) == 0;
-}
-
-static int launch_wgrad1x1_stream(WgradArgs& a, float* dw, float* db, float* workspace, hipStream_t st) {
+// a.nsplit: the grid (one partial per workgroup), ct: 16-channel output tiles per wave -- both from wgrad_fill_plan
+static int launch_wgrad1x1_stream(WgradArgs& a, int ct, float* dw, float* db, hipStream_t st) {
     Wg1x1Args k{};
     k.x = a.src[0].p;
     k.x_bs = a.src[0].bs;
@@ -1293,13 +1287,11 @@ static int launch_wgrad1x1_stream(WgradArgs& a, float* dw, float* db, float* wor
     k.HW = a.H * a.W;
     k.hw16 = k.HW / 16;
     k.chunks = (long long)a.B * k.hw16;
-    int grid = WG1X1_BLOCKS;
-    if ((long long)grid * 4 > k.chunks) grid = (int)((k.chunks + 3) / 4);
-    a.nsplit = grid;
-    a.partial_w = k.partial_w = workspace;
-    a.partial_b = k.partial_b = db ? workspace + (long long)grid * a.cout * 32 : nullptr;
+    const int grid = a.nsplit;
+    k.partial_w = a.partial_w;
+    k.partial_b = a.partial_b;
     ynet_note_launch(1, 4);
-    if (a.cout <= 16) hipLaunchKernelGGL(wgrad1x1_stream_kernel<1>, dim3(grid), dim3(256), 0, st, k);
+    if (ct == 1) hipLaunchKernelGGL(wgrad1x1_stream_kernel<1>, dim3(grid), dim3(256), 0, st, k);
     else hipLaunchKernelGGL(wgrad1x1_stream_kernel<2>, dim3(grid), dim3(256), 0, st, k);
     int rc = ynet_check_launch("conv2d_wgrad(1x1)");
     if (rc) return rc;
@@ -1349,39 +1341,44 @@ static int launch_wgrad_roll(WgradArgs& a, float* dw, float* db, hipStream_t st)
 
 // Rolling-row kernel: W % 32 == 0, H even, and enough strip segments of >= 4 two-row steps for the persistent workgroups
 // (16 / 8 / 4 steps: the longest that still gives three segments per workgroup; a segment start costs one extra row pair)
-static bool wgrad_roll_plan(WgradArgs& a) {
+// p: the two-row plan (tiles, channel blocks, nsplit); on success nsplit / seg / nseg_y / nsegs are the rolling-row launch's
+static bool wgrad_roll_plan(YnetWgradPlan& p, int B, int H, int W, int cin, bool masked) {
     static const int on = getenv("YNET_WGRAD_ROLL") ? atoi(getenv("YNET_WGRAD_ROLL")) : 1;
     static const int forced = getenv("YNET_WGRAD_SEG") ? atoi(getenv("YNET_WGRAD_SEG")) : 0;
-    if (!on || (a.W % 32) != 0 || (a.H & 1) != 0) return false;
-    const int tiles_y = a.H / 2, strips = a.B * (a.W / 32);
+    if (!on || (W % 32) != 0 || (H & 1) != 0) return false;
+    const int tiles_y = H / 2, strips = B * (W / 32);
+    int nsplit = p.nsplit;
     // without the mask tile three workgroups fit a CU (51 KB each): with two, 27 % of the MFMA slots stay empty even when no DMA
     // is issued at all (YNET_WGRAD_DEBUG=1) -- the waves of a workgroup meet at a barrier every 144 MFMAs
     static const int wg3 = getenv("YNET_WGRAD_WG3") ? atoi(getenv("YNET_WGRAD_WG3")) : 1;
-    if (a.mask == nullptr && wg3) {
-        const int blocks = a.co_blks * ceil_div(a.cin, 32);
+    if (!masked && wg3) {
+        const int blocks = p.co_blks * ceil_div(cin, 32);
         int n = 768 / blocks;
         if (n < 1) n = 1;
-        if (n > a.ntiles) n = a.ntiles;
-        a.nsplit = n;
+        if (n > p.ntiles) n = p.ntiles;
+        nsplit = n;
     }
     int seg = 0;
     for (int s : {16, 8, 4})
-        if (seg == 0 && (long long)strips * ceil_div(tiles_y, s) >= 3ll * a.nsplit) seg = s;
-    if (seg == 0 && (long long)strips * ceil_div(tiles_y, 4) >= a.nsplit) seg = 4;
+        if (seg == 0 && (long long)strips * ceil_div(tiles_y, s) >= 3ll * nsplit) seg = s;
+    if (seg == 0 && (long long)strips * ceil_div(tiles_y, 4) >= nsplit) seg = 4;
     if (forced > 0) seg = forced;
     if (seg == 0 || tiles_y < 2) return false;
-    static const int debug = getenv("YNET_WGRAD_DEBUG") ? atoi(getenv("YNET_WGRAD_DEBUG")) : 0;
-    a.debug = debug;
-    a.seg = seg;
-    a.nseg_y = ceil_div(tiles_y, seg);
-    a.nsegs = strips * a.nseg_y;
-    if (a.nsplit > a.nsegs) a.nsplit = a.nsegs;
+    p.seg = seg;
+    p.nseg_y = ceil_div(tiles_y, seg);
+    p.nsegs = strips * p.nseg_y;
+    p.nsplit = nsplit > p.nsegs ? p.nsegs : nsplit;
     return true;
+}
+
+static int wgrad_roll_debug() {
+    static const int debug = getenv("YNET_WGRAD_DEBUG") ? atoi(getenv("YNET_WGRAD_DEBUG")) : 0;
+    return debug;
 }
 
 template <int KS>
 static int launch_wgrad(WgradArgs& a, float* dw, float* db, hipStream_t st) {
-    a.ci_blks = ceil_div(a.cin, WgCfg<KS>::CIB);
+    static_assert(WgCfg<KS>::CIB == (KS == 5 ? 6 : 32), "wgrad_cib: the plan's input-channel block is the kernel's");
     return a.mask ? launch_wgrad_m<KS, true>(a, dw, db, st) : launch_wgrad_m<KS, false>(a, dw, db, st);
 }
 
@@ -1403,6 +1400,42 @@ static int wgrad_plan(int B, int H, int W, int cout, int cin, int K, int th, int
     if (nsplit > resident) nsplit = resident;
     *nsplit_out = nsplit;
     return tiles;
+}
+
+// 1x1, one 32-channel source, <= 32 output channels, no mask, whole 16-pixel chunks, 16-byte aligned planes
+static const int WG1X1_BLOCKS = 512;
+static bool wgrad1x1_stream_ok(int H, int W, int cout, int cin, int nsrc, int K, bool masked, bool aligned) {
+    static const int on = getenv("YNET_WGRAD_1X1_STREAM") ? atoi(getenv("YNET_WGRAD_1X1_STREAM")) : 1;
+    return on && K == 1 && nsrc == 1 && cin == 32 && cout <= 32 && !masked && ((long long)H * W) % 16 == 0 && aligned;
+}
+
+// The whole dispatch of ynet_conv2d_wgrad: which kernel, its tiles, channel blocks and split, and the floats of workspace the launch writes.
+// aligned: every plane (sources, dy, mask) on a 16-byte boundary with a batch stride % 4 == 0.  ynet_conv2d_wgrad launches what this fills in and
+// ynet_conv2d_wgrad_plan reports it.
+static void wgrad_fill_plan(int B, int H, int W, int cout, int cin, int nsrc, int K, bool masked, bool aligned, bool want_bias, YnetWgradPlan& p) {
+    p = YnetWgradPlan{};
+    const bool dma = wgrad_dma_shape(W, K) && aligned;
+    const int th = dma ? 2 : 4;      // rows per tile (one-row tiles: 3 workgroups per CU, more halo traffic -- measured equal)
+    p.rows = th;
+    p.tiles_x = ceil_div(W, 32);
+    p.tiles_y = ceil_div(H, th);
+    p.ntiles = wgrad_plan(B, H, W, cout, cin, K, th, &p.nsplit);
+    p.co_blks = ceil_div(cout, 32);
+    p.ci_blks = ceil_div(cin, wgrad_cib(K));
+    if (dma) {
+        p.kernel = wgrad_roll_plan(p, B, H, W, cin, masked) ? 3 : 2;      // (may change nsplit: up to the 768 resident workgroups the workspace is sized for)
+    } else if (wgrad1x1_stream_ok(H, W, cout, cin, nsrc, K, masked, aligned)) {
+        p.kernel = 4;
+        p.rows = 0;
+        const long long chunks = (long long)B * (((long long)H * W) / 16);
+        int grid = WG1X1_BLOCKS;
+        if ((long long)grid * 4 > chunks) grid = (int)((chunks + 3) / 4);
+        p.nsplit = grid;          // one partial per workgroup
+        p.ct = cout <= 16 ? 1 : 2;
+    } else {
+        p.kernel = 1;
+    }
+    p.partial_floats = (long long)p.nsplit * cout * cin * K * K + (want_bias ? (long long)p.nsplit * cout : 0);
 }
 
 extern "C" {
@@ -1441,36 +1474,56 @@ int ynet_conv2d_wgrad(const float* const* src, const int* src_c, const long long
     a.H = H;
     a.W = W;
     a.cout = cout;
-    bool dma = wgrad_dma_shape(W, K);
+    bool aligned = true;
     {
         auto misaligned = [](const void* p, long long bs) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0 || (bs & 3) != 0; };
-        for (int i = 0; i < nsrc; ++i) dma = dma && !misaligned(src[i], src_bs[i]);
-        dma = dma && !misaligned(dy, dy_bs) && (mask == nullptr || !misaligned(mask, mask_bs));
+        for (int i = 0; i < nsrc; ++i) aligned = aligned && !misaligned(src[i], src_bs[i]);
+        aligned = aligned && !misaligned(dy, dy_bs) && (mask == nullptr || !misaligned(mask, mask_bs));
     }
-    const int th = dma ? 2 : 4;      // rows per tile (one-row tiles: 3 workgroups per CU, more halo traffic -- measured equal)
-    a.tiles_x = ceil_div(W, 32);
-    a.tiles_y = ceil_div(H, th);
-    a.ntiles = wgrad_plan(B, H, W, cout, a.cin, K, th, &a.nsplit);
-    a.co_blks = ceil_div(cout, 32);
+    YnetWgradPlan p;
+    wgrad_fill_plan(B, H, W, cout, a.cin, nsrc, K, mask != nullptr, aligned, db != nullptr, p);
+    a.tiles_x = p.tiles_x;
+    a.tiles_y = p.tiles_y;
+    a.ntiles = p.ntiles;
+    a.nsplit = p.nsplit;
+    a.co_blks = p.co_blks;
+    a.ci_blks = p.ci_blks;
+    a.seg = p.seg;
+    a.nseg_y = p.nseg_y;
+    a.nsegs = p.nsegs;
     a.partial_w = workspace;
-    hipStream_t st = (hipStream_t)stream;
-    if (dma) {
-        a.ci_blks = ceil_div(a.cin, 32);
-        const int nsplit_dma = a.nsplit;
-        const bool roll = wgrad_roll_plan(a);      // (may change nsplit: up to the 768 resident workgroups the workspace is sized for)
-        if (!roll) a.nsplit = nsplit_dma;
-        a.partial_b = db ? workspace + (long long)a.nsplit * cout * a.cin * K * K : nullptr;
-        if (roll) return mask ? launch_wgrad_roll<true>(a, dw, db, st) : launch_wgrad_roll<false>(a, dw, db, st);
-        return mask ? launch_wgrad_dma<true, 2>(a, dw, db, st) : launch_wgrad_dma<false, 2>(a, dw, db, st);
-    }
     a.partial_b = db ? workspace + (long long)a.nsplit * cout * a.cin * K * K : nullptr;
-    if (wgrad1x1_stream_ok(a, K)) return launch_wgrad1x1_stream(a, dw, db, workspace, st);
+    hipStream_t st = (hipStream_t)stream;
+    switch (p.kernel) {
+        case 3:
+            a.debug = wgrad_roll_debug();
+            return mask ? launch_wgrad_roll<true>(a, dw, db, st) : launch_wgrad_roll<false>(a, dw, db, st);
+        case 2: return mask ? launch_wgrad_dma<true, 2>(a, dw, db, st) : launch_wgrad_dma<false, 2>(a, dw, db, st);
+        case 4: return launch_wgrad1x1_stream(a, p.ct, dw, db, st);
+        default: break;
+    }
     switch (K) {
         case 1: return launch_wgrad<1>(a, dw, db, st);
         case 3: return launch_wgrad<3>(a, dw, db, st);
         case 5: return launch_wgrad<5>(a, dw, db, st);
         default: ynet_set_error("conv2d_wgrad: kernel size %d not supported (1, 3, 5)", K); return 1;
     }
+}
+
+// what ynet_conv2d_wgrad would launch for this problem: host code only
+int ynet_conv2d_wgrad_plan(int B, int H, int W, int cout, const int* src_c, int nsrc, int K, int masked, int aligned, int want_bias,
+                           YnetWgradPlan* out) {
+    YNET_REQUIRE(out != nullptr && src_c != nullptr, "conv2d_wgrad_plan: null pointer");
+    YNET_REQUIRE(nsrc >= 1 && nsrc <= YNET_MAX_SRC, "conv2d_wgrad_plan: 1..%d sources supported", YNET_MAX_SRC);
+    YNET_REQUIRE(B > 0 && H > 0 && W > 0 && cout > 0, "conv2d_wgrad_plan: empty problem");
+    YNET_REQUIRE(K == 1 || K == 3 || K == 5, "conv2d_wgrad_plan: kernel size %d not supported (1, 3, 5)", K);
+    int cin = 0;
+    for (int i = 0; i < nsrc; ++i) {
+        YNET_REQUIRE(src_c[i] > 0, "conv2d_wgrad_plan: source %d is empty", i);
+        cin += src_c[i];
+    }
+    wgrad_fill_plan(B, H, W, cout, cin, nsrc, K, masked != 0, aligned != 0, want_bias != 0, *out);
+    return 0;
 }
 
 }  // extern "C"

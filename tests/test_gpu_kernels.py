@@ -207,10 +207,13 @@ ROLL_WGRAD_CASES = [
     # B, H, W, [source channels], cout, ReLU mask, bias -- maps with enough 32-column strips for the rolling-row kernel
     (4, 128, 256, [6, 8], 32, True, True),      # encoder.stages.0.0: two sources, 14 channels (spare waves take K-step residues)
     (8, 64, 128, [32, 16], 32, True, False),    # 48 input channels = a full and a half channel block, segments of 4 steps
-    (8, 64, 64, [64], 64, False, True),         # 2 x 2 blocks, first and last tile column only
+    (8, 64, 64, [64], 64, False, True),         # 2 x 2 blocks without a mask: 192 workgroups want 192 segments, B 8 has 128 -- the two-row LDS-DMA tiles (kernel 2)
     (4, 256, 128, [32], 16, True, True),        # half an output block
-    (2, 256, 256, [32], 32, False, False),      # segments of 16 steps; interior tile columns
+    (2, 256, 256, [32], 32, False, False),      # one block without a mask: 768 workgroups want 768 segments, B 2 has 512 -- the two-row LDS-DMA tiles (kernel 2)
+    (12, 64, 64, [64], 64, False, True),        # 2 x 2 blocks on the unmasked rolling-row kernel: 192 segments of 4 steps, first and last tile column only
+    (3, 256, 256, [32], 32, False, False),      # one block on the unmasked rolling-row kernel: 768 segments of 4 steps; interior tile columns
 ]
+ROLL_WGRAD_KERNEL = [3, 3, 2, 3, 2, 3, 3]        # what ynet_conv2d_last_launch(1) must note for each (tests/test_wgrad_cases_host.py asks the plan the same)
 
 
 @pytest.mark.parametrize("B,H,W,cs,cout,relu,bias", ROLL_WGRAD_CASES)
@@ -229,7 +232,9 @@ def test_conv2d_wgrad_rolling_rows(dev, B, H, W, cs, cout, relu, bias):
     y.backward(gy)
     xd, yd, gyd = [x.to(dev) for x in xs], y.detach().to(dev), gy.to(dev)
     mask = (yd.data_ptr(), cout * H * W) if relu else None
+    ops._lib().ynet_conv2d_last_launch(1)
     dw, db = ops.conv2d_wgrad_raw(xd, gyd, mask, w.to(dev), bias)
+    assert ops._lib().ynet_conv2d_last_launch(1) == ROLL_WGRAD_KERNEL[ROLL_WGRAD_CASES.index((B, H, W, cs, cout, relu, bias))]
     close(dw, wc.grad, rtol=1e-4, scale_rel=1e-5, msg="dW")
     if bias:
         close(db, bc.grad, rtol=1e-4, scale_rel=1e-5, msg="db")

@@ -36,6 +36,38 @@ int main() {
                         acc += ynet_conv2d_wgrad_workspace_floats(b, h, w, cout, 32, k);
                     }
                 }
+    {   // ynet_conv2d_wgrad_plan: the dispatch of ynet_conv2d_wgrad without a launch; what it says the launch writes fits the workspace formula
+        const int one_src[6][4] = {{1}, {14}, {32}, {33}, {65}, {130}};
+        const int cat2[2] = {6, 8}, cat4[4] = {16, 16, 8, 2};
+        YnetWgradPlan p;
+        auto sweep = [&](const int* sc, int nsrc, int cout, int k) {
+            int cin = 0;
+            for (int i = 0; i < nsrc; ++i) cin += sc[i];
+            for (int b : {1, 2, 5, 12, 16, 768})
+                for (int h : {1, 2, 4, 5, 10, 18, 34, 64, 128})
+                    for (int w : {1, 4, 32, 35, 36, 64, 96, 100})
+                        for (int flags = 0; flags < 8; ++flags) {      // masked, aligned, want_bias
+                            if (ynet_conv2d_wgrad_plan(b, h, w, cout, sc, nsrc, k, flags & 1, (flags >> 1) & 1, (flags >> 2) & 1, &p) != 0 || p.kernel < 1 || p.kernel > 4 ||
+                                p.nsplit < 1 || p.partial_floats <= 0 || p.partial_floats > ynet_conv2d_wgrad_workspace_floats(b, h, w, cout, cin, k)) {
+                                fprintf(stderr, "conv2d_wgrad_plan: B %d %dx%d cin %d cout %d K %d flags %d: kernel %d nsplit %d, %lld floats\n", b, h, w, cin, cout, k, flags,
+                                        p.kernel, p.nsplit, p.partial_floats);
+                                ++failures;
+                            }
+                            acc += p.kernel + p.nsplit + p.seg + p.ct;
+                        }
+        };
+        for (int k : {1, 3, 5})
+            for (int cout : {1, 3, 16, 17, 32, 33, 65, 130}) {
+                for (const int* sc : one_src) sweep(sc, 1, cout, k);
+                sweep(cat2, 2, cout, k);
+                sweep(cat4, 4, cout, k);
+            }
+        EXPECT_REJECT(ynet_conv2d_wgrad_plan(1, 4, 4, 4, cat2, 2, 7, 0, 1, 1, &p));        // kernel size 7
+        EXPECT_REJECT(ynet_conv2d_wgrad_plan(1, 4, 4, 4, cat2, 9, 3, 0, 1, 1, &p));        // 9 sources
+        EXPECT_REJECT(ynet_conv2d_wgrad_plan(1, 0, 4, 4, cat2, 2, 3, 0, 1, 1, &p));        // H = 0
+        EXPECT_REJECT(ynet_conv2d_wgrad_plan(1, 4, 4, 4, cat2, 2, 3, 0, 1, 1, nullptr));   // no plan to fill
+        EXPECT_REJECT(ynet_conv2d_wgrad_plan(1, 4, 4, 4, nullptr, 2, 3, 0, 1, 1, &p));
+    }
     acc += ynet_bce_workspace_bytes() + ynet_pred_bce_workspace_bytes() + ynet_comm_handle_bytes();
     if (acc <= 0) ++failures;
 
