@@ -641,6 +641,40 @@ int ynet_map_class_mass(const float* x, long long batch_stride, const unsigned c
                         long long B, int C, int H, int W, int n_classes, float temperature, float* mass /* [B*C][n_classes] */,
                         void* stream);
 
+/* Credible regions of the goal map: the SHARPNESS of the distribution the goals are sampled from -- sigmoid(pred_goal_map / temperature),
+ * every plane normalised (utils/evaluate.py:128-131, utils/image_utils.py:110-135) -- beside the calibration that ynet_map_likelihood's
+ * hpd measures (the reference only draws the maps).  Per plane (b, c) of x [B][C][H][W] (batch stride `batch_stride` elements, so a
+ * channel slice needs no copy), with z = x / T, w = sigmoid(z), Z = sum w, and per level q_l of the HOST array `levels` (n_levels
+ * values, read during the call; they travel in the kernel's argument block; q = the fp32 level taken to fp64):
+ *   threshold [B][C][L] = tau_q: the LARGEST logit value present in the plane with  sum over {i : x_i >= tau} of w_i  >=  q * Z
+ *   area      [B][C][L] = #{i : x_i >= tau_q}              (int32) the q-credible region: the smallest set of whole plateaus holding q
+ *   mass      [B][C][L] = (sum over {x_i >= tau_q} of w_i) / Z     >= q up to rounding
+ * Membership is decided on the raw fp32 logits as IEEE values, exactly as hpd decides it: a plateau enters or stays out as a whole,
+ * -0.0 == +0.0 (a threshold on that plateau is returned as +0.0), denormals are not flushed, +inf is an ordinary largest value.  So
+ * area == #{x >= threshold} holds exactly, and for any pixel g: x_g >= tau_q implies hpd_g <= mass_q, x_g < tau_q implies hpd_g > mass_q.
+ * One launch, one workgroup per plane (more than 65535 planes are fine: B * C <= 4194303), 64-bit offsets, the plane read from HBM
+ * once and four more times through the caches: a mass-weighted radix select over the monotone 32-bit keys of the logits, eight bits
+ * per pass; 24 KB of LDS.  Planes that start on a 16-byte boundary and hold a multiple of 4 pixels are read in 16-byte vectors, any
+ * other plane element by element (decided per plane).  w is fp32, formed exactly as ynet_map_likelihood forms it.
+ * Arithmetic: masses are summed as 64-bit INTEGERS, trunc(w * 2^(s - e)) with s = YNET_MAP_CREDIBLE_FRAC_BITS = 40 and
+ * e = floor(log2(largest w of the plane)) -- a power-of-two scaling, exact.  Integer sums do not depend on the order of the adds: two
+ * runs give the same bits, and no floating-point atomic is used.  Every scaled w is below 2^(s + 1), so a sum over n pixels is below
+ * n * 2^41: n <= YNET_MAP_CREDIBLE_MAX_PIXELS = 2^22 = 4194304 (2048 x 2048; Y-Net-Mod's 512 x 512 maps are 2^18) keeps it below
+ * 2^63.  Truncation drops less than 2^(e - s) <= 2^-s * Z per pixel, so every share S / Z moves by less than n * 2^-s / (1 - n * 2^-s)
+ * < n * 2^-39: 2^-21 at 512 x 512, 2^-23 at 256 x 256.  The comparison against q * Z is made in fp64 on the integer sums.
+ * Rules: a plane that holds a NaN logit: area = -1, threshold = mass = NaN, *status |= 1 (device int, zero it first).  Z == 0 (all
+ * -inf, or every sigmoid below fp32's range): area = 0, threshold = mass = NaN, no flag.  A -inf pixel (w = 0) is never a member.
+ * A constant plane: area = H * W at every level.
+ * Refused (non-zero, ynet_last_error) before any launch: null x, levels, area, threshold, mass or status; n_levels outside
+ * 1 .. YNET_MAP_CREDIBLE_MAX_LEVELS; a level outside the open interval (0, 1) or not above the one before it; temperature <= 0, not
+ * finite, or below 2.95e-39 (where 1 / T is not); B, C, H or W < 1; H * W > YNET_MAP_CREDIBLE_MAX_PIXELS; batch_stride < C * H * W;
+ * B * C > 4194303. */
+#define YNET_MAP_CREDIBLE_MAX_LEVELS 8
+#define YNET_MAP_CREDIBLE_FRAC_BITS 40
+#define YNET_MAP_CREDIBLE_MAX_PIXELS 4194304
+int ynet_map_credible(const float* x, long long batch_stride, long long B, int C, int H, int W, const float* levels, int n_levels,
+                      float temperature, int* area /* [B*C][n_levels] */, float* threshold, float* mass, int* status, void* stream);
+
 /* ---- heat-map construction -------------------------------------------------------------------- */
 /* get_patch + torch.stack (utils/image_utils.py:40-63; utils/train_epoch.py:63-78;
  * utils/evaluate.py:112-114,250-253): out[n] = tmpl[SH/2 - ry : +H, SW/2 - rx : +W] with

@@ -173,6 +173,17 @@ def compliance_report(df_metrics, images):
     return "\n".join(lines)
 
 
+def sharpness_report_of(df_metrics, images, resize_factor):
+    """The lines test(return_sharpness=...) prints per round, one per level (utils.sharpness.sharpness_report), from evaluate()'s
+    area<pct>_goal / inside<pct>_goal columns; every agent brings the size of its own scene's map."""
+    from ..utils.sharpness import sharpness_report
+    names = [c[len("area"):-len("_goal")] for c in df_metrics.columns if c.startswith("area") and c.endswith("_goal")]
+    pixels = {sid: int(images[sid].shape[-2]) * int(images[sid].shape[-1]) for sid in df_metrics["sceneId"].unique()}
+    return sharpness_report([float(n) / 100.0 for n in names], df_metrics[[f"inside{n}_goal" for n in names]].to_numpy(),
+                            df_metrics[[f"area{n}_goal" for n in names]].to_numpy(),
+                            np.array([pixels[sid] for sid in df_metrics["sceneId"]], dtype=np.float64), resize_factor)
+
+
 class YNetTrainer:
     def __init__(self, params, device=None):
         self.params = params
@@ -297,19 +308,24 @@ class YNetTrainer:
         return self.val_ADE, self.val_FDE
 
     # ------------------------------------------------------------------------------------------
-    def test(self, df_test, image_path, return_preds=False, return_samples=False, return_likelihood=False, return_compliance=False):
+    def test(self, df_test, image_path, return_preds=False, return_samples=False, return_likelihood=False, return_compliance=False,
+             return_sharpness=False):
         """``return_likelihood`` (not in the reference): evaluate() also scores the goal-map distribution against the ground truth
         (df_metrics columns nll, nll_goal, entropy_goal, hpd_goal) and every round prints its mean NLL and calibration error.
         ``return_compliance`` (not in the reference): evaluate() also reports where in the scene the goals go (df_metrics columns
         goal_mass_<k>, gt_goal_class, sample_goal_rate_<k>) and every round prints one line per semantic class: the mean goal mass,
-        the mean sampled-goal rate and the share of ground-truth goals on the class, beside the share of the map the class covers."""
+        the mean sampled-goal rate and the share of ground-truth goals on the class, beside the share of the map the class covers.
+        ``return_sharpness`` (not in the reference; False, True = (0.5, 0.9), or a tuple of levels): evaluate() also reports the size of
+        the goal map's credible regions (df_metrics columns area<pct>_goal, inside<pct>_goal) and every round prints one line per level:
+        how often the ground-truth goal lies inside the region (calibration) beside the region's mean and median area (sharpness)."""
         return self._test(df_test, image_path, return_preds=return_preds, return_samples=return_samples,
-                          return_likelihood=return_likelihood, return_compliance=return_compliance, **self.params)
+                          return_likelihood=return_likelihood, return_compliance=return_compliance, return_sharpness=return_sharpness,
+                          **self.params)
 
     def _test(self, df_test, image_path, dataset_name, resize_factor, batch_size, n_round, obs_len, pred_len,
               waypoints, n_goal, n_traj, temperature, rel_threshold, use_TTST, use_CWS, CWS_params,
               use_raw_data=False, return_preds=False, return_samples=False, network=None, swap_semantic=False,
-              return_likelihood=False, return_compliance=False, **kwargs):
+              return_likelihood=False, return_compliance=False, return_sharpness=False, **kwargs):
         test_images, test_loader, self.homo_mat = self.prepare_data(
             df_test, image_path, dataset_name, "test", obs_len, pred_len, resize_factor, use_raw_data)
         model = self.model.to(self.device)
@@ -324,7 +340,7 @@ class YNetTrainer:
                 "test", n_goal, n_traj, obs_len, batch_size, resize_factor, temperature, use_TTST, use_CWS,
                 rel_threshold, CWS_params, return_preds=return_preds, return_samples=return_samples,
                 network=network, swap_semantic=swap_semantic, dp=self.dp, return_likelihood=return_likelihood,
-                return_compliance=return_compliance)
+                return_compliance=return_compliance, return_sharpness=return_sharpness)
             list_metrics.append(df_metrics)
             list_trajs.append(trajs_dict)
             print(f"Round {e}: \nTest ADE: {test_ADE} \nTest FDE: {test_FDE}")
@@ -335,6 +351,8 @@ class YNetTrainer:
                 print(f"Test NLL: {df_metrics['nll'].mean()} \nTest goal ECE: {ece}")
             if return_compliance:
                 print(compliance_report(df_metrics, test_images))
+            if return_sharpness:
+                print(sharpness_report_of(df_metrics, test_images, resize_factor))
             self.eval_ADE.append(test_ADE)
             self.eval_FDE.append(test_FDE)
         avg_ade = sum(self.eval_ADE) / len(self.eval_ADE)

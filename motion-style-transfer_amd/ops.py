@@ -2939,8 +2939,73 @@ def map_class_mass(x: torch.Tensor, labels: torch.Tensor, n_classes: int, temper
     return out
 
 
+_credible_status = {}
+MAP_MAX_LEVELS = 8                  # YNET_MAP_CREDIBLE_MAX_LEVELS of include/ynet_hip.h
+MAP_CREDIBLE_MAX_PIXELS = 1 << 22   # YNET_MAP_CREDIBLE_MAX_PIXELS
+CREDIBLE_OUTPUTS = ("area", "threshold", "mass")
+
+
+def credible_levels(levels, what: str = "map_credible") -> np.ndarray:
+    """A host sequence of credible levels as the kernel takes them: a contiguous fp32 array of 1 .. MAP_MAX_LEVELS values inside the
+    open interval (0, 1), strictly ascending after the conversion to fp32; anything else is refused."""
+    if torch.is_tensor(levels):
+        if levels.is_cuda:
+            raise TypeError(f"{what}: the levels are read on the host at call time; pass a host sequence, not a device tensor")
+        levels = levels.detach().numpy()
+    q64 = np.asarray(levels, dtype=np.float64).reshape(-1)
+    if not 1 <= q64.size <= MAP_MAX_LEVELS:
+        raise ValueError(f"{what}: {q64.size} levels, expected 1 .. {MAP_MAX_LEVELS}")
+    q = np.ascontiguousarray(q64.astype(np.float32))
+    if not ((q > 0) & (q < 1)).all():      # (false for a NaN)
+        raise ValueError(f"{what}: the levels {q64.tolist()} must lie inside the open interval (0, 1) in fp32")
+    if not (np.diff(q) > 0).all():
+        raise ValueError(f"{what}: the levels {q64.tolist()} must ascend strictly in fp32")
+    return q
+
+
+def map_credible(x: torch.Tensor, levels, temperature: float = 1.0):
+    """Credible regions of the distribution `sampling` draws from (ynet_map_credible; utils/evaluate.py:128-131,
+    utils/image_utils.py:110-135): per plane of x [B, C, H, W], p = sigmoid(x / T) normalised to sum 1, and per level q of the host
+    sequence ``levels`` (1 .. 8 values in (0, 1), strictly ascending), the smallest set of whole logit plateaus that holds q of p.
+    -> dict of [B, C, L] device tensors: ``threshold`` (float32; the region is {x >= threshold}, and the value compares equal to a logit
+    of the plane), ``area`` (int32, its number of pixels) and ``mass`` (float32, the share of p it holds: >= q up to rounding).
+    One launch; a channel view such as x[:, -1:] is read in place.  Not differentiable.  Two calls give the same bits.
+    A plane that holds a NaN logit: area -1, NaN threshold and mass, and the next check_credible_status() raises.  A plane whose
+    weights are all 0: area 0, NaN threshold and mass."""
+    q = credible_levels(levels)
+    t, c, bs = _plane_desc(x.detach() if torch.is_tensor(x) else x, "map_credible")
+    B, _, H, W = t.shape
+    if not (float(temperature) > 0 and np.isfinite(float(temperature))):
+        raise ValueError(f"map_credible: temperature {temperature!r} must be positive and finite")
+    if H * W > MAP_CREDIBLE_MAX_PIXELS:
+        raise ValueError(f"map_credible: a plane of {H}x{W} has more than the {MAP_CREDIBLE_MAX_PIXELS} pixels the integer sums hold")
+    dev = t.device
+    out = {"area": torch.empty((B, c, q.size), device=dev, dtype=torch.int32),
+           "threshold": torch.empty((B, c, q.size), device=dev, dtype=torch.float32),
+           "mass": torch.empty((B, c, q.size), device=dev, dtype=torch.float32)}
+    st = _status_flag(_credible_status, dev)
+    lib = _lib()
+    L.check(lib.ynet_map_credible(t.data_ptr(), bs, B, c, H, W, q.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), int(q.size),
+                                  float(temperature), out["area"].data_ptr(), out["threshold"].data_ptr(), out["mass"].data_ptr(),
+                                  st.data_ptr(), _stream()), lib)
+    return out
+
+
+def check_credible_status(raise_error: bool = True) -> bool:
+    """Raise if a map_credible call met a plane that holds a NaN (checked at a sync point); the flag is cleared.
+    raise_error=False: report it instead (-> True if one did)."""
+    hit = False
+    for dev, st in _credible_status.items():
+        if int(st.item()) != 0:
+            st.zero_()
+            hit = True
+    if hit and raise_error:
+        raise RuntimeError("map_credible: a plane holds a NaN logit (no region: its area is -1)")
+    return hit
+
+
 _modes_status = {}
-MAX_MODES = 64      # ynet_map_modes takes up to the MAX_SAMPLES of the ranking kernel
+MAX_MODES = 64     # ynet_map_modes takes up to the MAX_SAMPLES of the ranking kernel
 
 
 def map_modes(x: torch.Tensor, n_modes: int, radius: int, temperature: float = 1.0, want_mass: bool = True):

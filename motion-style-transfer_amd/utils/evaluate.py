@@ -16,6 +16,7 @@ import torch
 from .. import ops
 from . import step_graph
 from .image_utils import SAMPLER, draw_seed, gather_patches, image2world, sampling, swap_pavement_terrain
+from .sharpness import inside_regions, level_name, sharpness_levels
 
 
 # YNET_SWEEP_STREAMS=0: the K-sample decoder passes of a batch run back to back on one stream
@@ -209,7 +210,7 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
              n_goal, n_traj, obs_len, batch_size, resize_factor=0.25, temperature=1, use_TTST=False, use_CWS=False,
              rel_thresh=0.002, CWS_params=None, return_preds=False, return_samples=False, network=None,
              swap_semantic=False, forced_samples=None, dp=None, max_effective_batch=256, forced_goals=None,
-             forced_ttst_samples=None, return_compliance=False, return_likelihood=False):
+             forced_ttst_samples=None, return_compliance=False, return_sharpness=False, return_likelihood=False):
     """utils/evaluate.py:37-315.  Extra keyword arguments (tests / data-parallel runs): ``forced_samples`` [K,B,nwp,2]
     per batch replaces every random draw, ``forced_goals`` [n_goal,B,1,2] per batch only the goal draw,
     ``forced_ttst_samples`` [10000,B,1,2] per batch the TTST draw; ``dp`` shards each batch over ranks.
@@ -225,7 +226,15 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
     (the share of the last step's distribution on class k), ``gt_goal_class`` (the class of the ground-truth goal pixel, -1
     outside the map) and ``sample_goal_rate_<k>`` (the fraction of the sampled goals on class k); with ``return_preds``
     trajs_dict gains ``class_mass_steps`` [N, pred_len, K].  One launch per batch; the sweep takes the branch ``return_preds``
-    takes, as for ``return_likelihood``."""
+    takes, as for ``return_likelihood``.
+    ``return_sharpness`` (False, True = (0.5, 0.9), or a tuple of 1 .. 8 ascending levels in (0, 1)) reports how LARGE the credible
+    regions of that distribution are, where ``hpd`` says how well calibrated (ops.map_credible): per level q
+    the smallest set of whole logit plateaus that holds q of the mass.  df_out gains ``area<pct>_goal`` (pixels of the resized map,
+    last step; -1 for a plane with a NaN) and ``inside<pct>_goal`` (1.0 / 0.0: the logit at the rounded ground-truth goal is >= the
+    region's threshold; NaN where it rounds outside the map) per level, <pct> = 100 q; with ``return_preds`` trajs_dict gains
+    ``area_steps`` (int32), ``threshold_steps`` and ``inside_steps``, each [N, pred_len, L].  One launch per batch; the sweep takes the
+    branch ``return_preds`` takes, as for ``return_likelihood``."""
+    sharp_levels = sharpness_levels(return_sharpness)      # (a bad level raises before anything runs)
     model.eval()
     waypoints = list(waypoints)
     n_wp = len(waypoints)
@@ -247,6 +256,8 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                 raise ValueError(f"evaluate(return_compliance=True): scene {sid} has {im.shape[0]} planes; the classes of at most "
                                  f"{MAX_CLASSES} planes are told apart")
 
+    sharp_lists = {k: [] for k in ("area", "threshold", "inside")} if sharp_levels is not None else None
+
     with torch.no_grad():
         # Every packed filter is (re)written HERE, on the caller's stream: the K-sample passes below run the trajectory decoder on two
         # side streams, and a filter packed lazily by the first pass on one of them (after a training epoch bumped the parameter
@@ -255,8 +266,10 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
         ops.refresh_filters(model)
         if return_likelihood:
             ops.check_likelihood_status()      # a report left pending by an earlier ops.map_likelihood call of the caller's is raised, not swallowed below
+        if sharp_levels is not None:
+            ops.check_credible_status()
         plain = (forced_samples is None and forced_goals is None and not use_TTST and not use_CWS and not return_preds
-                 and not return_samples and dataset_name != "eth" and not return_likelihood and not return_compliance)
+                 and not return_samples and dataset_name != "eth" and not return_likelihood and not return_compliance and sharp_levels is None)
         sa = getattr(model, "softargmax_", None)
         hooked = sa is not None and (sa._forward_hooks or sa._forward_pre_hooks)
         graphs = None
@@ -331,6 +344,10 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                             labels, n_cls = scene_label_maps[scene_id]
                             comp = {"mass": ops.map_class_mass(pred_goal_map, labels, n_cls, temperature),
                                     "gt_class": point_classes(gt_future[:, -1], labels)}
+                        if sharp_levels is not None:      # every step's plane at every level: one launch
+                            sharp = ops.map_credible(pred_goal_map, sharp_levels, temperature)
+                            sharp = {"area": sharp["area"], "threshold": sharp["threshold"],
+                                     "inside": inside_regions(pred_goal_map, gt_future, sharp["threshold"])}
 
                         if forced_samples is not None:
                             waypoint_samples = forced_samples[b][:, lo:lo + n_local].to(device)
@@ -370,6 +387,10 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                             comp = {"mass": torch.zeros((0, trajectory.shape[1] - obs_len, n_cls), device=device),
                                     "gt_class": torch.zeros(0, device=device, dtype=torch.int64),
                                     "rate": torch.zeros((0, n_cls), device=device, dtype=torch.float64)}
+                        if sharp_levels is not None:
+                            empty = (0, trajectory.shape[1] - obs_len, len(sharp_levels))
+                            sharp = {"area": torch.zeros(empty, device=device, dtype=torch.int32), "threshold": torch.zeros(empty, device=device),
+                                     "inside": torch.zeros(empty, device=device)}
                     if dp is not None:
                         sizes = dp.shard_sizes(n_global)
                         ade, fde = dp.gather_rows(ade, sizes), dp.gather_rows(fde, sizes)
@@ -377,11 +398,17 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                             like = {k: dp.gather_rows(v, sizes) for k, v in like.items()}
                         if return_compliance:
                             comp = {k: dp.gather_rows(v, sizes) for k, v in comp.items()}
+                        if sharp_levels is not None:
+                            sharp = {k: dp.gather_rows(v, sizes) for k, v in sharp.items()}
                     ade_list.append(ade.cpu().numpy())
                     fde_list.append(fde.cpu().numpy())
                     if return_compliance:
                         for k, v in comp.items():
                             comp_lists[k].append(v.cpu().numpy())
+                    if sharp_levels is not None:
+                        for k, v in sharp.items():
+                            sharp_lists[k].append(v.cpu().numpy())
+                        ops.check_credible_status()      # (synchronised by the copies above: a NaN logit in a goal map raises here)
                     if return_likelihood:
                         for k, v in like.items():
                             like_lists[k].append(v.cpu().numpy())
@@ -418,9 +445,17 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
         df_out["gt_goal_class"] = np.concatenate(comp_lists["gt_class"], axis=0)
         for k in range(rates.shape[-1]):
             df_out[f"sample_goal_rate_{k}"] = rates[:, k]
+    if sharp_levels is not None:
+        sharp_steps = {k: np.concatenate(v, axis=0) for k, v in sharp_lists.items()}      # [N, pred_len, L] each
+        for l, q in enumerate(sharp_levels):
+            df_out[f"area{level_name(q)}_goal"] = sharp_steps["area"][:, -1, l]
+            df_out[f"inside{level_name(q)}_goal"] = sharp_steps["inside"][:, -1, l]
     if return_preds:
         for key, value in trajs_dict.items():
             trajs_dict[key] = np.concatenate(value, axis=0)
+        if sharp_levels is not None:
+            for k, v in sharp_steps.items():
+                trajs_dict[k + "_steps"] = v
         if return_compliance:
             trajs_dict["class_mass_steps"] = mass_steps
         if return_likelihood:

@@ -16,8 +16,9 @@ models.style_bank.StyleBank, one call.
 ``predict_modes`` is predict() with no draw at all: the goals are the modes of the goal map's logits under greedy non-maximum
 suppression (ops.map_modes), each with the probability mass it claims.
 
-``predict_with_entropy`` and ``predict_with_compliance`` are predict() plus one read-out of the goal map each: its entropy
-(DESIGN.md section 4.10), and the share of it on every semantic class of the scene (ops.map_class_mass).
+``predict_with_entropy``, ``predict_with_compliance`` and ``predict_with_regions`` are predict() plus one read-out of the goal map
+each: its entropy, the share of it on every semantic class of the scene (ops.map_class_mass, DESIGN.md
+section 4.13), and its credible regions (ops.map_credible).
 """
 import functools
 import inspect
@@ -112,12 +113,14 @@ def _mode_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, n_modes,
 
 def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
               use_TTST, use_CWS, rel_thresh, CWS_params, network, swap_semantic, batch_size, max_effective_batch, forced_samples, return_maps,
-              return_entropy, modes=None, return_compliance=False):
+              return_entropy, modes=None, return_compliance=False, regions=None):
     """The one body of predict(), predict_with_entropy(), predict_styles() and predict_modes(), on arguments that went through _validated.
     modes              None, or (n_modes, radius): the way-points are not drawn but read off the goal map (_mode_waypoints; then
                        n_goal = n_modes, n_traj = 1, and the results gain ``mode_mass`` and ``mode_logit``)
     return_compliance  the results gain ``goal_class_mass`` [N, pred_len, K]: one ops.map_class_mass launch per chunk against
                        utils.compliance.scene_labels(scene_image), the classes of the scene as given (before ``swap_semantic``)
+    regions            None, or the credible levels (ops.credible_levels): the results gain ``region_area`` (int32), ``region_threshold``
+                       and ``region_mass`` [N, pred_len, L]: one ops.map_credible launch per chunk
     refresh()          packs the filters the chunks will read, on the caller's stream, before the decoder passes fan out over two (see
                        evaluate()): ops.refresh_filters(model), or a StyleBank's refresh() for its shadows and the shared layers
     chunk_plan(b, n)   for the n agents from b on -> (perm, pred_features): ``perm`` None, or the order the chunk runs in (row j of the
@@ -133,7 +136,8 @@ def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template
     model.eval()
     out = {k: [] for k in ["trajectories", "waypoints", "scores", "order"] + (["goal_map", "goal_sigmoid_map"] if return_maps else [])
            + (["entropy"] if return_entropy else []) + (["mode_mass", "mode_logit"] if modes is not None else [])
-           + (["goal_class_mass"] if return_compliance else [])}
+           + (["goal_class_mass"] if return_compliance else [])
+           + (["region_area", "region_threshold", "region_mass"] if regions is not None else [])}
     try:
         with torch.no_grad():
             refresh()
@@ -187,6 +191,9 @@ def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template
                     out["entropy"].append(ops.map_likelihood(pred_goal_map, None, temperature, want=("entropy",))["entropy"])
                 if return_compliance:
                     out["goal_class_mass"].append(ops.map_class_mass(pred_goal_map, labels, scene_image.shape[0], temperature))
+                if regions is not None:
+                    for k, v in ops.map_credible(pred_goal_map, regions, temperature).items():
+                        out["region_" + k].append(v)
 
                 trajs_samples = _decoder_passes(model, features, waypoint_samples, input_template, n, n_wp, H, W, max_effective_batch, device)
                 ranking = (wp_sigmoid, waypoint_samples, trajs_samples.contiguous(), resize_factor)
@@ -198,6 +205,8 @@ def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template
                 ops.check_patch_status()      # (the ranking call waited for the chunk: a window that left the template raises here)
                 if perm is not None:
                     ops.check_gather_status()
+                if regions is not None:
+                    ops.check_credible_status()      # (a NaN logit in a goal map of the chunk raises here)
                 if modes is not None:
                     nan = ops.check_modes_status(raise_error=False)
                     short = torch.nonzero(found["short"]).flatten().tolist()
@@ -227,7 +236,8 @@ def predict(model, scene_image, observed, input_template, waypoints, n_goal, n_t
        ``order`` [N, K] int32 (row r is sample order[:, r] of the sweep), and with ``return_maps`` ``goal_map`` [N, pred_len, H, W]
        and ``goal_sigmoid_map`` as evaluate(return_samples=True) stores them.
        predict_with_entropy() is this call plus ``entropy`` [N, pred_len]: how spread out every step's goal-map distribution is;
-       predict_with_compliance() is this call plus ``goal_class_mass`` [N, pred_len, K]: the share of it on every class of the scene."""
+       predict_with_compliance() is this call plus ``goal_class_mass`` [N, pred_len, K]: the share of it on every class of the scene;
+       predict_with_regions() is this call plus the credible regions of it, ``region_area`` / ``region_threshold`` / ``region_mass``."""
     return _predict(False, **locals())
 
 
@@ -257,6 +267,23 @@ def predict_with_compliance(*args, return_entropy=False, **kwargs):
     return _predict(bool(return_entropy), **bound.arguments, return_compliance=True)
 
 
+def predict_with_regions(*args, levels=(0.5, 0.9), **kwargs):
+    """predict() with the same arguments, and three more results, each [N, pred_len, L] (device tensors): per future step and per level
+    q of ``levels`` (keyword only; 1 .. 8 strictly ascending values inside (0, 1)) the q-credible region of the goal-map distribution --
+    sigmoid(pred_goal_map / T) normalised per plane, what `sampling` draws from --, the smallest set of whole logit plateaus that holds
+    q of the mass: ``region_threshold`` (float32; the region is {goal_map >= threshold}: utils.sharpness.region_mask draws it),
+    ``region_area`` (int32, its pixels in the resized map) and ``region_mass`` (float32, the share it holds, >= q up to rounding).
+    One ops.map_credible launch per chunk; the values are the ones evaluate(return_sharpness=levels) reports
+    as ``area_steps`` and ``threshold_steps``.  It needs no ground truth and no draw; every other result is predict()'s, bit for bit.
+    A goal map that holds a NaN raises RuntimeError at the chunk's sync point.
+    (A function of its own and not a keyword of predict(), as predict_with_entropy(): predict()'s parameter list is pinned by
+    tests/test_predict_host.py, and predict_styles mirrors it.)"""
+    regions = tuple(float(q) for q in ops.credible_levels(levels, "predict_with_regions"))
+    bound = _PREDICT_SIGNATURE.bind(*args, **kwargs)
+    bound.apply_defaults()
+    return _predict(False, **bound.arguments, regions=regions)
+
+
 def _predict(return_entropy, model, scene_image, observed, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
              use_TTST, use_CWS, rel_thresh, CWS_params, batch_size, forced_samples, **options):
     """predict() / predict_with_entropy(): no permutation, the model's own features and filters"""
@@ -283,6 +310,7 @@ def predict_styles(bank, scene_image, observed, style, input_template, waypoints
     every other argument and every result as for predict(); the results are in the caller's order and carry ``style_index`` [N] (int64).
     The goal-map entropy of predict_with_entropy() is out of scope here for now: there is no predict_styles form of it.
     Neither is the scene compliance of predict_with_compliance(): out of scope here for now.
+    Nor are the credible regions of predict_with_regions().
 
     Each chunk (``batch_size`` agents of the caller's order; it may hold any subset of the styles) is stable-sorted by style index on
     the host -- the labels are host data.  ynet_gather_rows builds the sorted observed coordinates and forced samples, and

@@ -277,6 +277,38 @@ int main() {
         EXPECT_REJECT(ynet_map_class_mass(cfp, 32, lab, 15, 2, 2, 4, 4, 6, 1.f, fp, nullptr));                           // label stride neither 0 nor a plane
         EXPECT_REJECT(ynet_map_class_mass(cfp, 4, lab, 0, 1ll << 29, 4, 1, 1, 6, 1.f, fp, nullptr));                     // 2^31 planes
     }
+    {   // the credible levels are read on the host: exactly n_levels of them (heap arrays of that length, so a read past them is seen)
+        float* q8 = new float[YNET_MAP_CREDIBLE_MAX_LEVELS];
+        float* q2 = new float[2];
+        for (int l = 0; l < YNET_MAP_CREDIBLE_MAX_LEVELS; ++l) q8[l] = 0.1f + 0.1f * l;
+        q2[0] = 0.5f, q2[1] = 0.9f;
+        int* ip = reinterpret_cast<int*>(dummy);
+        EXPECT_REJECT(ynet_map_credible(cfp, 16, 0, 1, 4, 4, q8, YNET_MAP_CREDIBLE_MAX_LEVELS, 1.f, ip, fp, fp, &status, nullptr));     // B < 1, found after all 8 were read
+        EXPECT_REJECT(ynet_map_credible(nullptr, 16, 1, 1, 4, 4, q2, 2, 1.f, ip, fp, fp, &status, nullptr));                            // no map
+        EXPECT_REJECT(ynet_map_credible(cfp, 16, 1, 1, 4, 4, nullptr, 2, 1.f, ip, fp, fp, &status, nullptr));                           // no levels
+        EXPECT_REJECT(ynet_map_credible(cfp, 16, 1, 1, 4, 4, q2, 2, 1.f, nullptr, fp, fp, &status, nullptr));                           // no outputs
+        EXPECT_REJECT(ynet_map_credible(cfp, 16, 1, 1, 4, 4, q2, 2, 1.f, ip, nullptr, fp, &status, nullptr));
+        EXPECT_REJECT(ynet_map_credible(cfp, 16, 1, 1, 4, 4, q2, 2, 1.f, ip, fp, nullptr, &status, nullptr));
+        EXPECT_REJECT(ynet_map_credible(cfp, 16, 1, 1, 4, 4, q2, 2, 1.f, ip, fp, fp, nullptr, nullptr));                                // no status flag
+        EXPECT_REJECT(ynet_map_credible(cfp, 16, 1, 1, 4, 4, q2, 0, 1.f, ip, fp, fp, &status, nullptr));                                // n_levels outside 1 .. 8
+        EXPECT_REJECT(ynet_map_credible(cfp, 16, 1, 1, 4, 4, q2, YNET_MAP_CREDIBLE_MAX_LEVELS + 1, 1.f, ip, fp, fp, &status, nullptr)); // (refused before a level is read)
+        q2[1] = 0.5f;
+        EXPECT_REJECT(ynet_map_credible(cfp, 16, 1, 1, 4, 4, q2, 2, 1.f, ip, fp, fp, &status, nullptr));                                // not ascending strictly
+        q2[1] = 1.f;
+        EXPECT_REJECT(ynet_map_credible(cfp, 16, 1, 1, 4, 4, q2, 2, 1.f, ip, fp, fp, &status, nullptr));                                // outside (0, 1)
+        q2[0] = 0.f, q2[1] = 0.9f;
+        EXPECT_REJECT(ynet_map_credible(cfp, 16, 1, 1, 4, 4, q2, 2, 1.f, ip, fp, fp, &status, nullptr));
+        q2[0] = 0.f / 0.f;
+        EXPECT_REJECT(ynet_map_credible(cfp, 16, 1, 1, 4, 4, q2, 2, 1.f, ip, fp, fp, &status, nullptr));
+        q2[0] = 0.5f;
+        EXPECT_REJECT(ynet_map_credible(cfp, 16, 1, 1, 4, 4, q2, 2, 0.f, ip, fp, fp, &status, nullptr));                                // temperature 0
+        EXPECT_REJECT(ynet_map_credible(cfp, 16, 1, 1, 4, 4, q2, 2, 1e-39f, ip, fp, fp, &status, nullptr));                             // a denormal: 1 / T overflows
+        EXPECT_REJECT(ynet_map_credible(cfp, 1ll << 23, 1, 1, 2048, 2049, q2, 2, 1.f, ip, fp, fp, &status, nullptr));                   // above the pixel cap
+        EXPECT_REJECT(ynet_map_credible(cfp, 31, 2, 2, 4, 4, q2, 2, 1.f, ip, fp, fp, &status, nullptr));                                // batch stride below the image
+        EXPECT_REJECT(ynet_map_credible(cfp, 4, 1ll << 22, 1, 1, 1, q2, 2, 1.f, ip, fp, fp, &status, nullptr));                         // too many planes
+        delete[] q8;
+        delete[] q2;
+    }
     {   // the sweep reads its temperatures on the host: exactly n_temps of them (a heap array of that length, so a read past it is seen)
         float* t32 = new float[YNET_SWEEP_MAX_TEMPS];
         float* t3 = new float[3];
