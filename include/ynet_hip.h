@@ -675,6 +675,50 @@ int ynet_map_class_mass(const float* x, long long batch_stride, const unsigned c
 int ynet_map_credible(const float* x, long long batch_stride, long long B, int C, int H, int W, const float* levels, int n_levels,
                       float temperature, int* area /* [B*C][n_levels] */, float* threshold, float* mass, int* status, void* stream);
 
+/* Scene occupancy of the goal map: the distributions the goals are sampled from -- sigmoid(pred_goal_map / temperature), every plane
+ * normalised (utils/evaluate.py:128-131, utils/image_utils.py:110-135) -- of ALL the agents of a scene, summed per step: where anybody
+ * will be, and which agents are forecast into the same place (the reference draws one agent's map at a time:
+ * evaluator/visualization.py plot_goal_output).  x [B][C][H][W] (batch stride `batch_stride` elements, so a channel slice needs no
+ * copy); group g (the agents of one scene) holds the rows offsets[g] .. offsets[g + 1] - 1 (`offsets`: DEVICE int32 [G + 1]; an empty
+ * group is legal).  The map is cut into cells of cell x cell pixels, Hc = ceil(H / cell), Wc = ceil(W / cell), the edge cells
+ * partial.  Per agent a and step c, with z = x / T, w = sigmoid(z), Z_a = sum w over the plane and m_a[cell] = (sum of w over the
+ * cell's pixels) / Z_a, and the agents taken as independent:
+ *   occupancy [G][C][Hc][Wc] = D = sum_a m_a                          the expected number of agents in the cell; sums to the group's size
+ *   any       [G][C][Hc][Wc] = 1 - prod_a (1 - m_a)                   the probability that the cell holds at least one agent  (or NULL)
+ *   conflict  [G][C]         = 1/2 sum_cells (D^2 - sum_a m_a^2)      the expected number of agent pairs that share a cell     (or NULL)
+ *   risk      [B][C]         = sum_cells m_a (D - m_a)                the expected number of OTHER agents in agent a's cell    (or NULL)
+ * so that sum_a risk_a = 2 * conflict up to rounding.  One call, three launches, no floating-point atomic: two runs give the same bits.
+ *   1. 1 / Z_a per plane in fp64, as ynet_map_class_mass forms Z (one read of x), into the workspace;
+ *   2. one workgroup per (g, c, tile of 64 patches); a thread owns a patch of max(4, cell) x cell pixels -- 4 / 2 / 1 / 1 whole cells --
+ *      and walks agents in row order.  Per agent and cell the fp32 sum s of w over the cell's pixels is taken in a fixed order,
+ *      m = (float)((double)s / Z_a); D, sum m^2 and prod (1 - m) are fp64 registers of that thread (m * m is exact in fp64).  The
+ *      workgroup's 1 / 2 / 4 / 8 waves take consecutive runs of the group's agents (a split that depends on the group's size alone)
+ *      and add their sums through LDS in wave order.  With `risk` a second walk over the same agents reads the tile again and forms
+ *      every agent's sum m (D - m);
+ *   3. the tile partials of every (g, c) and (a, c) are added in a fixed order in fp64.
+ * So a group of one agent has conflict == 0 and risk == 0 exactly, and so have agents whose weights share no cell.  w is fp32, formed
+ * exactly as ynet_map_likelihood forms it.  Planes that start on a 16-byte boundary, with W % 4 == 0, are read in 16-byte vectors, any
+ * other plane element by element (decided per plane); both paths add the same terms in the same order, so the results do not depend
+ * on where a plane starts.  An agent's terms do not depend on which other groups are in the call.  64-bit offsets; more than 65535
+ * (g, c, tile) workgroups are fine.
+ * Rules: a plane with a NaN logit, or with Z == 0, makes its (g, c) NaN in all four outputs -- its occupancy and any cells, its
+ * conflict, the risk of every agent of g at c -- and *status |= 1 (device int, zero it first); other groups and other steps keep
+ * their bits.  A -inf logit adds 0; +inf is weight 1; sigmoids below fp32's normal range count as 0.  An empty group:
+ * occupancy = any = conflict = 0.  A group whose bounds are not 0 <= lo <= hi <= B: *status |= 2, its occupancy, any and conflict are
+ * NaN, and so is the risk of the rows from lo on up to the next group's (as far as such bounds name rows at all); no entry of
+ * `offsets` is ever used as an address outside x.  risk rows that belong to no group are not written.
+ * `workspace`: ynet_map_occupancy_workspace_bytes(...) bytes on the device, 8-byte aligned, contents irrelevant (-1 and
+ * ynet_last_error for a shape the call would refuse).
+ * Refused (non-zero, ynet_last_error) before any launch: null x, offsets, occupancy, workspace or status; cell not one of 1, 2, 4,
+ * 8; temperature <= 0 or not finite (or below 2.95e-39, where 1 / T is not); B, C, H, W or G < 1; batch_stride < C * H * W;
+ * H * W > 2^31 - 2048; B * C or G * C * tiles >= 2^31.
+ * Out of scope: proximity within a radius instead of cell sharing, the trajectory decoder's maps, hipGraph capture of the call. */
+#define YNET_MAP_OCCUPANCY_MAX_CELL 8
+long long ynet_map_occupancy_workspace_bytes(long long B, int C, int H, int W, long long G, int cell);
+int ynet_map_occupancy(const float* x, long long batch_stride, const int* offsets /* device, [G + 1] */, long long B, long long G,
+                       int C, int H, int W, int cell, float temperature, float* occupancy, float* any /* or null */,
+                       float* conflict /* or null */, float* risk /* or null */, void* workspace, int* status, void* stream);
+
 /* ---- heat-map construction -------------------------------------------------------------------- */
 /* get_patch + torch.stack (utils/image_utils.py:40-63; utils/train_epoch.py:63-78;
  * utils/evaluate.py:112-114,250-253): out[n] = tmpl[SH/2 - ry : +H, SW/2 - rx : +W] with

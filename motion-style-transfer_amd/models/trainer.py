@@ -393,9 +393,10 @@ class YNetTrainer:
 
     def _predict(self, df_obs, image_path, dataset_name, resize_factor, obs_len, waypoints, n_goal, n_traj, temperature,
                  batch_size=None, rel_threshold=0.002, use_TTST=False, use_CWS=False, CWS_params=None, use_raw_data=False,
-                 network=None, swap_semantic=False, return_maps=False, bank=None, style_column=None, modes=None, **kwargs):
+                 network=None, swap_semantic=False, return_maps=False, bank=None, style_column=None, modes=None, occupancy=None,
+                 **kwargs):
         import pandas as pd
-        from ..utils.predict import MAX_SAMPLES, predict, predict_modes, predict_styles
+        from ..utils.predict import MAX_SAMPLES, predict, predict_modes, predict_styles, predict_with_occupancy
         if dataset_name.lower() == "eth":
             raise NotImplementedError("predict: ETH/UCY forecasts are in world coordinates (homographies read from data files): "
                                       "out of the MI355X hot path, as in prepare_data")
@@ -435,6 +436,9 @@ class YNetTrainer:
                 res = predict_modes(model, images[scene_id], observed, input_template, waypoints, *modes, obs_len, resize_factor, temperature,
                                     CWS_params=CWS_params if use_CWS else None, network=network, swap_semantic=swap_semantic,
                                     batch_size=batch_size, return_maps=return_maps)
+            elif occupancy is not None:      # the cell edge: predict() plus the scene's occupancy; every scene runs as one chunk
+                res = predict_with_occupancy(model, images[scene_id], observed, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor,
+                                             temperature, cell=occupancy, **{**kw, "batch_size": None})
             elif bank is None:
                 res = predict(model, images[scene_id], observed, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature, **kw)
             else:
@@ -484,6 +488,17 @@ class YNetTrainer:
         if not 1 <= n_modes <= 64 or radius < 0:      # (before any scene is prepared; utils.predict.predict_modes says why)
             raise ValueError(f"predict_modes: n_modes = {n_modes} (1 .. 64), radius = {radius} (>= 0)")
         return self._predict(df_obs, image_path_or_images, return_maps=return_maps, modes=(n_modes, radius), **self.params)
+
+    def predict_occupancy(self, df_obs, image_path_or_images, cell=4):
+        """predict() plus the question a forecast of a SCENE is asked first: where will anybody be at step t, and which agents are
+        forecast into the same place (utils.predict.predict_with_occupancy).  ``df_obs`` and ``image_path_or_images`` as for
+        predict(); ``cell``: the edge of a cell in pixels of the resized map (1, 2, 4 or 8).  Every scene runs as one chunk whatever
+        ``batch_size`` the parameters hold: the pairs across two chunks would be lost.
+        -> as predict(); every scene's dict carries ``occupancy`` and ``occupancy_any`` [pred_len, Hc, Wc], ``conflict`` [pred_len]
+        and ``risk`` [N, pred_len] (utils.occupancy.conflict_report ranks the agents per step)."""
+        if cell not in (1, 2, 4, 8):      # (before any scene is prepared)
+            raise ValueError(f"predict_occupancy: cell = {cell!r}, expected one of (1, 2, 4, 8)")
+        return self._predict(df_obs, image_path_or_images, occupancy=int(cell), **self.params)
 
     # ------------------------------------------------------------------------------------------
     def forward_test(self, df_test, image_path, set_input, noisy_std_frac):

@@ -3004,6 +3004,100 @@ def check_credible_status(raise_error: bool = True) -> bool:
     return hit
 
 
+_occupancy_status = {}
+_occupancy_offsets = {}             # (device, the bounds' bytes) -> the bounds on the device: a repeated layout is uploaded once
+OCCUPANCY_CELLS = (1, 2, 4, 8)      # up to YNET_MAP_OCCUPANCY_MAX_CELL of include/ynet_hip.h
+OCCUPANCY_OUTPUTS = ("occupancy", "any", "conflict", "risk")
+
+
+def occupancy_offsets(group_sizes, B: int, what: str = "map_occupancy") -> np.ndarray:
+    """A host sequence of group sizes as the kernel takes it: the int32 row bounds [G + 1] of G >= 1 groups (an empty group is legal)
+    that together hold exactly the B rows; None is one group of all rows.  Anything else is refused."""
+    if group_sizes is None:
+        return np.array([0, B], dtype=np.int32)
+    if torch.is_tensor(group_sizes):
+        if group_sizes.is_cuda:
+            raise TypeError(f"{what}: the group sizes are read on the host at call time; pass a host sequence, not a device tensor")
+        group_sizes = group_sizes.detach().numpy()
+    raw = np.asarray(group_sizes).reshape(-1)
+    if raw.size < 1 or raw.dtype.kind not in "iu":
+        raise ValueError(f"{what}: group_sizes must be a non-empty sequence of integers, got {group_sizes!r}")
+    sizes = raw.astype(np.int64)
+    if (sizes < 0).any():
+        raise ValueError(f"{what}: a group size is negative: {sizes.tolist() if sizes.size <= 16 else str(sizes[:16].tolist()) + ' ...'}")
+    if int(sizes.sum()) != B:
+        raise ValueError(f"{what}: the group sizes sum to {int(sizes.sum())}, the map holds {B} rows")
+    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+
+
+def map_occupancy(x: torch.Tensor, group_sizes=None, cell: int = 1, temperature: float = 1.0, want: Sequence[str] = OCCUPANCY_OUTPUTS):
+    """Scene occupancy of the distributions `sampling` draws from (ynet_map_occupancy; utils/evaluate.py:128-131,
+    utils/image_utils.py:110-135): per plane of x [B, C, H, W], p = sigmoid(x / T) normalised to sum 1; the rows of x are the agents,
+    ``group_sizes`` (host sequence; None: one group of all rows) cuts them into G scenes of consecutive rows, an empty one is legal.
+    The map is cut into cells of ``cell`` x ``cell`` pixels (1, 2, 4 or 8; Hc = ceil(H / cell), Wc = ceil(W / cell), the edge cells
+    partial); m_a is agent a's share of p inside a cell, the agents are taken as independent.
+    -> dict of float32 device tensors, one per name in ``want`` ("occupancy" is always there):
+       ``occupancy`` [G, C, Hc, Wc]  sum_a m_a: the expected number of agents in the cell (a plane sums to the group's size)
+       ``any``       [G, C, Hc, Wc]  1 - prod_a (1 - m_a): the probability that the cell holds at least one agent
+       ``conflict``  [G, C]          1/2 sum_cells (D^2 - sum_a m_a^2): the expected number of agent pairs that share a cell
+       ``risk``      [B, C]          sum_cells m_a (D - m_a): the expected number of other agents in agent a's cell
+    One call; the map is read about twice (three times with "risk").  A channel view such as x[:, -1:] is read in place.  Not
+    differentiable.  Two calls give the same bits.  A plane that holds a NaN logit, or whose weights are all 0, makes every result of
+    its group at that step NaN, and the next check_occupancy_status() raises."""
+    want = tuple(want)
+    if len(set(want)) != len(want) or any(w not in OCCUPANCY_OUTPUTS for w in want):
+        raise ValueError(f"map_occupancy: want {want!r}: a selection of {OCCUPANCY_OUTPUTS} is expected")
+    if cell not in OCCUPANCY_CELLS:
+        raise ValueError(f"map_occupancy: cell = {cell!r}, expected one of {OCCUPANCY_CELLS}")
+    cell = int(cell)
+    if not (float(temperature) > 0 and np.isfinite(float(temperature))):
+        raise ValueError(f"map_occupancy: temperature {temperature!r} must be positive and finite")
+    t, c, bs = _plane_desc(x.detach() if torch.is_tensor(x) else x, "map_occupancy")
+    B, _, H, W = t.shape
+    if B < 1 or c < 1 or H < 1 or W < 1:
+        raise ValueError(f"map_occupancy: nothing to sum in a map of shape {tuple(t.shape)}")
+    offsets = occupancy_offsets(group_sizes, B)
+    G = offsets.size - 1
+    dev = t.device
+    Hc, Wc = -(-H // cell), -(-W // cell)
+    out = {"occupancy": torch.empty((G, c, Hc, Wc), device=dev, dtype=torch.float32)}
+    if "any" in want:
+        out["any"] = torch.empty((G, c, Hc, Wc), device=dev, dtype=torch.float32)
+    if "conflict" in want:
+        out["conflict"] = torch.empty((G, c), device=dev, dtype=torch.float32)
+    if "risk" in want:
+        out["risk"] = torch.empty((B, c), device=dev, dtype=torch.float32)
+    ptr = {w: (out[w].data_ptr() if w in out else None) for w in OCCUPANCY_OUTPUTS}
+    lib = _lib()
+    need = lib.ynet_map_occupancy_workspace_bytes(B, c, H, W, G, cell)
+    if need < 0:
+        L.check(1, lib)
+    ws = torch.empty(((need + 7) // 8,), device=dev, dtype=torch.float64)
+    key = (dev, offsets.tobytes())
+    off_dev = _occupancy_offsets.get(key)
+    if off_dev is None:
+        if len(_occupancy_offsets) >= 16:
+            _occupancy_offsets.clear()
+        off_dev = _occupancy_offsets[key] = torch.from_numpy(offsets).to(dev)
+    st = _status_flag(_occupancy_status, dev)
+    L.check(lib.ynet_map_occupancy(t.data_ptr(), bs, off_dev.data_ptr(), B, G, c, H, W, cell, float(temperature), ptr["occupancy"], ptr["any"],
+                                   ptr["conflict"], ptr["risk"], ws.data_ptr(), st.data_ptr(), _stream()), lib)
+    return out
+
+
+def check_occupancy_status(raise_error: bool = True) -> bool:
+    """Raise if a map_occupancy call met a plane that holds a NaN or whose weights are all 0 (checked at a sync point); the flag is
+    cleared.  raise_error=False: report it instead (-> True if one did)."""
+    hit = False
+    for dev, st in _occupancy_status.items():
+        if int(st.item()) != 0:
+            st.zero_()
+            hit = True
+    if hit and raise_error:
+        raise RuntimeError("map_occupancy: a plane holds a NaN logit or has no weight at all (its group is NaN at that step)")
+    return hit
+
+
 _modes_status = {}
 MAX_MODES = 64     # ynet_map_modes takes up to the MAX_SAMPLES of the ranking kernel
 

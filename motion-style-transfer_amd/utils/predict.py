@@ -18,7 +18,9 @@ suppression (ops.map_modes), each with the probability mass it claims (DESIGN.md
 
 ``predict_with_entropy``, ``predict_with_compliance`` and ``predict_with_regions`` are predict() plus one read-out of the goal map
 each: its entropy, the share of it on every semantic class of the scene (ops.map_class_mass, DESIGN.md
-section 4.13), and its credible regions (ops.map_credible).
+section 4.13), and its credible regions (ops.map_credible).  ``predict_with_occupancy`` is predict() plus the
+one read-out that is about the scene and not about an agent: the agents' goal maps summed per step, and the expected conflicts between
+them (ops.map_occupancy).
 """
 import functools
 import inspect
@@ -113,7 +115,7 @@ def _mode_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, n_modes,
 
 def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
               use_TTST, use_CWS, rel_thresh, CWS_params, network, swap_semantic, batch_size, max_effective_batch, forced_samples, return_maps,
-              return_entropy, modes=None, return_compliance=False, regions=None):
+              return_entropy, modes=None, return_compliance=False, occupancy=None, regions=None):
     """The one body of predict(), predict_with_entropy(), predict_styles() and predict_modes(), on arguments that went through _validated.
     modes              None, or (n_modes, radius): the way-points are not drawn but read off the goal map (_mode_waypoints; then
                        n_goal = n_modes, n_traj = 1, and the results gain ``mode_mass`` and ``mode_logit``)
@@ -121,6 +123,9 @@ def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template
                        utils.compliance.scene_labels(scene_image), the classes of the scene as given (before ``swap_semantic``)
     regions            None, or the credible levels (ops.credible_levels): the results gain ``region_area`` (int32), ``region_threshold``
                        and ``region_mass`` [N, pred_len, L]: one ops.map_credible launch per chunk
+    occupancy          None, or the cell edge (1, 2, 4, 8): the results gain ``occupancy`` and ``occupancy_any`` [pred_len, Hc, Wc],
+                       ``conflict`` [pred_len] and ``risk`` [N, pred_len] from one ops.map_occupancy call; the scene must run as ONE
+                       chunk (the pairs across two chunks would be lost), anything else is refused before the model is touched
     refresh()          packs the filters the chunks will read, on the caller's stream, before the decoder passes fan out over two (see
                        evaluate()): ops.refresh_filters(model), or a StyleBank's refresh() for its shadows and the shared layers
     chunk_plan(b, n)   for the n agents from b on -> (perm, pred_features): ``perm`` None, or the order the chunk runs in (row j of the
@@ -131,13 +136,17 @@ def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template
     n_wp, K = len(waypoints), n_goal * n_traj
     N = obs.shape[0]
     step = N if batch_size is None else int(batch_size)
+    if occupancy is not None and step < N:
+        raise ValueError(f"{name}: the occupancy of a scene needs all its {N} agents in one chunk, batch_size = {step} would split them "
+                         f"(the pairs across two chunks would be lost); pass batch_size=None or >= {N}")
     device = next(model.parameters()).device
     was_training = model.training
     model.eval()
     out = {k: [] for k in ["trajectories", "waypoints", "scores", "order"] + (["goal_map", "goal_sigmoid_map"] if return_maps else [])
            + (["entropy"] if return_entropy else []) + (["mode_mass", "mode_logit"] if modes is not None else [])
            + (["goal_class_mass"] if return_compliance else [])
-           + (["region_area", "region_threshold", "region_mass"] if regions is not None else [])}
+           + (["region_area", "region_threshold", "region_mass"] if regions is not None else [])
+           + (["occupancy", "occupancy_any", "conflict", "risk"] if occupancy is not None else [])}
     try:
         with torch.no_grad():
             refresh()
@@ -194,6 +203,12 @@ def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template
                 if regions is not None:
                     for k, v in ops.map_credible(pred_goal_map, regions, temperature).items():
                         out["region_" + k].append(v)
+                if occupancy is not None:      # (one group: the chunk is the scene)
+                    occ = ops.map_occupancy(pred_goal_map, None, occupancy, temperature)
+                    out["occupancy"].append(occ["occupancy"][0])
+                    out["occupancy_any"].append(occ["any"][0])
+                    out["conflict"].append(occ["conflict"][0])
+                    out["risk"].append(occ["risk"])
 
                 trajs_samples = _decoder_passes(model, features, waypoint_samples, input_template, n, n_wp, H, W, max_effective_batch, device)
                 ranking = (wp_sigmoid, waypoint_samples, trajs_samples.contiguous(), resize_factor)
@@ -207,6 +222,8 @@ def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template
                     ops.check_gather_status()
                 if regions is not None:
                     ops.check_credible_status()      # (a NaN logit in a goal map of the chunk raises here)
+                if occupancy is not None:
+                    ops.check_occupancy_status()
                 if modes is not None:
                     nan = ops.check_modes_status(raise_error=False)
                     short = torch.nonzero(found["short"]).flatten().tolist()
@@ -237,7 +254,8 @@ def predict(model, scene_image, observed, input_template, waypoints, n_goal, n_t
        and ``goal_sigmoid_map`` as evaluate(return_samples=True) stores them.
        predict_with_entropy() is this call plus ``entropy`` [N, pred_len]: how spread out every step's goal-map distribution is;
        predict_with_compliance() is this call plus ``goal_class_mass`` [N, pred_len, K]: the share of it on every class of the scene;
-       predict_with_regions() is this call plus the credible regions of it, ``region_area`` / ``region_threshold`` / ``region_mass``."""
+       predict_with_regions() is this call plus the credible regions of it, ``region_area`` / ``region_threshold`` / ``region_mass``;
+       predict_with_occupancy() is this call plus the scene's ``occupancy`` / ``occupancy_any`` / ``conflict`` / ``risk``."""
     return _predict(False, **locals())
 
 
@@ -284,6 +302,31 @@ def predict_with_regions(*args, levels=(0.5, 0.9), **kwargs):
     return _predict(False, **bound.arguments, regions=regions)
 
 
+def predict_with_occupancy(*args, cell=4, **kwargs):
+    """predict() with the same arguments, and four more results (device tensors, float32) about the SCENE, not about one agent: the
+    goal-map distributions of all N agents -- sigmoid(pred_goal_map / T) normalised per plane, what `sampling` draws from -- summed per
+    future step over cells of ``cell`` x ``cell`` pixels of the resized map (keyword only; 1, 2, 4 or 8), the agents taken as
+    independent:
+      ``occupancy``      [pred_len, Hc, Wc]  the expected number of agents in the cell (every step sums to N)
+      ``occupancy_any``  [pred_len, Hc, Wc]  the probability that the cell holds at least one agent
+      ``conflict``       [pred_len]          the expected number of agent pairs that share a cell
+      ``risk``           [N, pred_len]       the expected number of other agents in the agent's cell (sums to 2 * conflict per step)
+    with Hc = ceil(H / cell), Wc = ceil(W / cell) (utils.occupancy: cell_grid, upsample_occupancy for overlays, conflict_report).
+    One ops.map_occupancy call on the goal map.  It needs no ground truth and no draw; every other result is
+    predict()'s, bit for bit.  The scene must run as ONE chunk: ``batch_size`` None or >= N.  Anything else raises ValueError, because
+    the pairs of agents that fall into different chunks would be lost.  A goal map that holds a NaN raises RuntimeError at the chunk's
+    sync point.
+    Out of scope for now: evaluate(), a predict_styles or predict_modes form, scenes split over chunks, proximity within a radius
+    instead of cell sharing, the trajectory decoder's maps, and capturing the call into a hipGraph.
+    (A function of its own and not a keyword of predict(), as predict_with_entropy(): predict()'s parameter list is pinned by
+    tests/test_predict_host.py, and predict_styles mirrors it.)"""
+    if cell not in ops.OCCUPANCY_CELLS:
+        raise ValueError(f"predict_with_occupancy: cell = {cell!r}, expected one of {ops.OCCUPANCY_CELLS}")
+    bound = _PREDICT_SIGNATURE.bind(*args, **kwargs)
+    bound.apply_defaults()
+    return _predict(False, **bound.arguments, occupancy=int(cell))
+
+
 def _predict(return_entropy, model, scene_image, observed, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
              use_TTST, use_CWS, rel_thresh, CWS_params, batch_size, forced_samples, **options):
     """predict() / predict_with_entropy(): no permutation, the model's own features and filters"""
@@ -310,7 +353,7 @@ def predict_styles(bank, scene_image, observed, style, input_template, waypoints
     every other argument and every result as for predict(); the results are in the caller's order and carry ``style_index`` [N] (int64).
     The goal-map entropy of predict_with_entropy() is out of scope here for now: there is no predict_styles form of it.
     Neither is the scene compliance of predict_with_compliance(): out of scope here for now.
-    Nor are the credible regions of predict_with_regions().
+    Nor are the credible regions of predict_with_regions(), nor the scene occupancy of predict_with_occupancy().
 
     Each chunk (``batch_size`` agents of the caller's order; it may hold any subset of the styles) is stable-sorted by style index on
     the host -- the labels are host data.  ynet_gather_rows builds the sorted observed coordinates and forced samples, and
@@ -353,7 +396,8 @@ def predict_modes(model, scene_image, observed, input_template, waypoints, n_mod
        sum to the covered share of its map -- and the raw logit of its peak.  With one way-point ``order`` is 0 .. n_modes - 1.
     An agent whose goal map gives fewer modes (non-finite logits) raises RuntimeError at the chunk's sync point.
     Out of scope for now: a predict_styles form, evaluate() over modes, sub-pixel refinement of the peak, capturing the call into
-    a hipGraph, and the scene compliance of predict_with_compliance() (the class mass of the goal map)."""
+    a hipGraph, the scene compliance of predict_with_compliance() (the class mass of the goal map), and the scene occupancy of
+    predict_with_occupancy()."""
     n_modes, radius = int(n_modes), int(radius)
     if not 1 <= n_modes <= MAX_SAMPLES:
         raise ValueError(f"predict_modes: n_modes = {n_modes}; the ranking kernel takes 1 .. {MAX_SAMPLES}")

@@ -309,6 +309,55 @@ int main() {
         delete[] q8;
         delete[] q2;
     }
+    {   // scene occupancy: the refusals (the offsets are device data: the host never reads them), and the workspace arithmetic over a small sweep
+        alignas(8) double wsbuf[1] = {0.0};
+        void* ws = wsbuf;
+        const int* off = &one;
+        EXPECT_REJECT(ynet_map_occupancy(nullptr, 16, off, 1, 1, 1, 4, 4, 2, 1.f, fp, fp, fp, fp, ws, &status, nullptr));             // no map
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 16, nullptr, 1, 1, 1, 4, 4, 2, 1.f, fp, fp, fp, fp, ws, &status, nullptr));             // no offsets
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 16, off, 1, 1, 1, 4, 4, 2, 1.f, nullptr, fp, fp, fp, ws, &status, nullptr));            // no occupancy
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 16, off, 1, 1, 1, 4, 4, 2, 1.f, fp, fp, fp, fp, nullptr, &status, nullptr));            // no workspace
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 16, off, 1, 1, 1, 4, 4, 2, 1.f, fp, fp, fp, fp, (char*)ws + 4, &status, nullptr));      // workspace off an 8-byte boundary
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 16, off, 1, 1, 1, 4, 4, 2, 1.f, fp, fp, fp, fp, ws, nullptr, nullptr));                 // no status flag
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 16, off, 1, 1, 1, 4, 4, 0, 1.f, fp, fp, fp, fp, ws, &status, nullptr));                 // cell outside {1, 2, 4, 8}
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 16, off, 1, 1, 1, 4, 4, 3, 1.f, fp, fp, fp, fp, ws, &status, nullptr));
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 16, off, 1, 1, 1, 4, 4, 2 * YNET_MAP_OCCUPANCY_MAX_CELL, 1.f, fp, fp, fp, fp, ws, &status, nullptr));
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 16, off, 1, 1, 1, 4, 4, 2, 0.f, fp, fp, fp, fp, ws, &status, nullptr));                 // temperature 0
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 16, off, 1, 1, 1, 4, 4, 2, 0.f / 0.f, fp, fp, fp, fp, ws, &status, nullptr));           // not finite
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 16, off, 1, 1, 1, 4, 4, 2, 1e-39f, fp, fp, fp, fp, ws, &status, nullptr));              // a denormal: 1 / T overflows
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 16, off, 0, 1, 1, 4, 4, 2, 1.f, fp, fp, fp, fp, ws, &status, nullptr));                 // B, G, C, H, W < 1
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 16, off, 1, 0, 1, 4, 4, 2, 1.f, fp, fp, fp, fp, ws, &status, nullptr));
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 16, off, 1, 1, 0, 4, 4, 2, 1.f, fp, fp, fp, fp, ws, &status, nullptr));
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 16, off, 1, 1, 1, 0, 4, 2, 1.f, fp, fp, fp, fp, ws, &status, nullptr));
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 16, off, 1, 1, 1, 4, 0, 2, 1.f, fp, fp, fp, fp, ws, &status, nullptr));
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 31, off, 2, 1, 2, 4, 4, 2, 1.f, fp, fp, fp, fp, ws, &status, nullptr));                 // batch stride below the image
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 1ll << 31, off, 1, 1, 1, 32768, 65536, 2, 1.f, fp, fp, fp, fp, ws, &status, nullptr));  // 2^31 pixels per plane
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 4, off, 1ll << 29, 1, 4, 1, 1, 2, 1.f, fp, fp, fp, fp, ws, &status, nullptr));          // 2^31 planes
+        EXPECT_REJECT(ynet_map_occupancy(cfp, 4, off, 1, 1ll << 29, 4, 1, 1, 2, 1.f, fp, fp, fp, fp, ws, &status, nullptr));          // 2^31 (g, c, tile) workgroups
+        const int cells[4] = {1, 2, 4, 8};
+        for (int ci = 0; ci < 4; ++ci) {
+            const int cell = cells[ci], pw = cell < 4 ? 4 : cell;
+            for (int H = 1; H <= 33; H += 4) {
+                for (int W = 1; W <= 70; W += 23) {
+                    for (long long B = 1; B <= 9; B += 4) {
+                        for (long long G = 1; G <= 3; ++G) {
+                            const long long T = ((long long)((W + pw - 1) / pw) * ((H + cell - 1) / cell) + 63) / 64;
+                            if (ynet_map_occupancy_workspace_bytes(B, 3, H, W, G, cell) != 8 * (B * 3 + G * 3 * T + B * 3 * T)) {
+                                fprintf(stderr, "map_occupancy_workspace_bytes(%lld, 3, %d, %d, %lld, %d)\n", B, H, W, G, cell);
+                                return 1;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        if (ynet_map_occupancy_workspace_bytes(0, 3, 4, 4, 1, 2) != -1 || ynet_map_occupancy_workspace_bytes(1, 3, 4, 4, 1, 3) != -1
+            || ynet_map_occupancy_workspace_bytes(1, 3, 4, 4, 0, 2) != -1 || ynet_map_occupancy_workspace_bytes(1, 1, 32768, 65536, 1, 1) != -1
+            || ynet_map_occupancy_workspace_bytes(1ll << 29, 4, 1, 1, 1, 1) != -1 || ynet_map_occupancy_workspace_bytes(1, 4, 1, 1, 1ll << 29, 1) != -1) {
+            fprintf(stderr, "map_occupancy_workspace_bytes: a refused shape got a size\n");
+            return 1;
+        }
+    }
     {   // the sweep reads its temperatures on the host: exactly n_temps of them (a heap array of that length, so a read past it is seen)
         float* t32 = new float[YNET_SWEEP_MAX_TEMPS];
         float* t3 = new float[3];
