@@ -6,24 +6,10 @@
 // flight per thread, and beside each one 4-byte load of the four labels.  Per-pixel terms are fp32 (sigmoid_term.h: the same z and the
 // same w as the likelihood kernels form); the running sums, the cross-wave combine and the division are fp64.  The public C ABI is
 // include/ynet_hip.h.
-#include "ynet_common.h"
-#include "sigmoid_term.h"
+#include "map_plane.h"
 #include "../../include/ynet_hip.h"
-#include <math.h>
 
 namespace {
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-template <bool DIVIDE>
-__device__ __forceinline__ float weight(float x, float inv_t, float t) {
-    const float z = tempered<DIVIDE>(x, inv_t, t);
-    return sigmoid_weight(z, sigmoid_term(z));
-}
 
 struct MassArgs {
     const float* x;
@@ -46,7 +32,7 @@ __global__ __launch_bounds__(256) void map_class_mass_kernel(const MassArgs a) {
     const long long plane = blockIdx.x;
     const long long row = plane / a.C;
     const int n = a.H * a.W;
-    const float* __restrict__ p = a.x + row * a.bs + (plane % a.C) * (long long)n;
+    const float* __restrict__ p = a.x + row * a.bs + (plane % a.C) * (long long)n;      // (plane_ptr, spelled out: see map_plane.h)
     const unsigned char* __restrict__ lab = a.labels + row * a.lbs;
     // running sums in fp64: sum w, and per class the sum of w over its pixels
     double sw = 0.0;
@@ -132,9 +118,8 @@ __global__ __launch_bounds__(256) void map_class_mass_kernel(const MassArgs a) {
     }
     __syncthreads();
     if (tid < K) {      // thread k: class k, the four waves' sums in the order Z takes them
-        const double Z = (ws[0][0] + ws[1][0]) + (ws[2][0] + ws[3][0]);
-        const double s = (ws[0][1 + tid] + ws[1][1 + tid]) + (ws[2][1 + tid] + ws[3][1 + tid]);
-        const bool bad = (wpoison[0] | wpoison[1] | wpoison[2] | wpoison[3]) != 0 || Z == 0.0;
+        const double Z = four_wave_sum(&ws[0][0], K + 1), s = four_wave_sum(&ws[0][1 + tid], K + 1);
+        const bool bad = four_wave_poison(wpoison) || Z == 0.0;
         a.mass[plane * K + tid] = bad ? __builtin_nanf("") : (float)(s / Z);
     }
 }
@@ -165,12 +150,9 @@ extern "C" int ynet_map_class_mass(const float* x, long long batch_stride, const
     YNET_REQUIRE(mass != nullptr, "map_class_mass: null output (mass)");
     YNET_REQUIRE(n_classes >= 1 && n_classes <= YNET_MAP_MAX_CLASSES, "map_class_mass: n_classes = %d, expected 1 .. %d", n_classes,
                  YNET_MAP_MAX_CLASSES);
-    YNET_REQUIRE(temperature > 0.f && temperature <= 3.0e38f && 1.f / temperature <= 3.0e38f,
-                 "map_class_mass: the temperature and its reciprocal must be positive and finite");
-    YNET_REQUIRE(B >= 1 && C >= 1 && H >= 1 && W >= 1, "map_class_mass: bad shape B=%lld C=%d %dx%d", B, C, H, W);
-    YNET_REQUIRE((long long)H * W <= (1ll << 31) - 2048, "map_class_mass: a plane of %dx%d is beyond the 32-bit pixel index", H, W);      // (i += 256 stays an int)
-    YNET_REQUIRE(batch_stride >= (long long)C * H * W, "map_class_mass: batch stride %lld below the %d planes of %dx%d of an image",
-                 batch_stride, C, H, W);
+    if (map_check_temperature("map_class_mass", temperature) || map_check_shape("map_class_mass", B, C, H, W) ||
+        map_check_pixel_index("map_class_mass", H, W) || map_check_batch_stride("map_class_mass", batch_stride, C, H, W))
+        return 1;
     YNET_REQUIRE(label_batch_stride == 0 || label_batch_stride >= (long long)H * W,
                  "map_class_mass: label batch stride %lld is neither 0 (one label plane for all rows) nor at least the %dx%d bytes of a plane",
                  label_batch_stride, H, W);

@@ -19,11 +19,9 @@
 // and exponent with shifts, so exact whatever the denormal mode.  Integer adds are order-free: LDS atomics give the same bits run
 // after run, the sub-bins of a bin add up to it exactly, and the walk of pass k + 1 is certain to find its crossing inside the bin
 // pass k chose.  The comparison against q * Z is fp64 (q: the fp32 level taken to fp64).
-#include "ynet_common.h"
-#include "sigmoid_term.h"
+#include "map_plane.h"
 #include "../../include/ynet_hip.h"
 #include <limits.h>
-#include <math.h>
 
 namespace {
 
@@ -49,12 +47,6 @@ __device__ __forceinline__ unsigned key_of(float x) {
 __device__ __forceinline__ float logit_of(unsigned u) {
     const int k = (int)(u ^ 0x80000000u);
     return __int_as_float(k >= 0 ? k : (k ^ 0x7fffffff));
-}
-
-template <bool DIVIDE>
-__device__ __forceinline__ float weight(float x, float inv_t, float t) {
-    const float z = tempered<DIVIDE>(x, inv_t, t);
-    return sigmoid_weight(z, sigmoid_term(z));
 }
 
 // w = mant * 2^(ex - 150), 0 <= mant < 2^24 (ex = 1 for a denormal)
@@ -120,7 +112,7 @@ __global__ __launch_bounds__(THREADS) void map_credible_kernel(const CredArgs a)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long plane = blockIdx.x;
     const int n = a.n, L = a.L;
-    const float* __restrict__ p = a.x + (plane / a.C) * a.bs + (plane % a.C) * (long long)n;
+    const float* __restrict__ p = a.x + (plane / a.C) * a.bs + (plane % a.C) * (long long)n;      // (plane_ptr, spelled out: see map_plane.h)
     const bool vec = (n & 3) == 0 && (((uintptr_t)p) & 15) == 0;
 
     // pass 0: the largest key, the NaN flag
@@ -302,13 +294,10 @@ extern "C" int ynet_map_credible(const float* x, long long batch_stride, long lo
         YNET_REQUIRE(l == 0 || levels[l] > levels[l - 1], "map_credible: the levels must ascend strictly (level %d = %g after %g)", l,
                      (double)levels[l], (double)levels[l - 1]);
     }
-    YNET_REQUIRE(temperature > 0.f && temperature <= 3.0e38f && 1.f / temperature <= 3.0e38f,
-                 "map_credible: the temperature and its reciprocal must be positive and finite");
-    YNET_REQUIRE(B >= 1 && C >= 1 && H >= 1 && W >= 1, "map_credible: bad shape B=%lld C=%d %dx%d", B, C, H, W);
+    if (map_check_temperature("map_credible", temperature) || map_check_shape("map_credible", B, C, H, W)) return 1;
     YNET_REQUIRE((long long)H * W <= YNET_MAP_CREDIBLE_MAX_PIXELS, "map_credible: a plane of %dx%d has more than the %d pixels the integer sums hold",
                  H, W, YNET_MAP_CREDIBLE_MAX_PIXELS);
-    YNET_REQUIRE(batch_stride >= (long long)C * H * W, "map_credible: batch stride %lld below the %d planes of %dx%d of an image",
-                 batch_stride, C, H, W);
+    if (map_check_batch_stride("map_credible", batch_stride, C, H, W)) return 1;
     YNET_REQUIRE(B <= MAX_PLANES && B * C <= MAX_PLANES, "map_credible: too many planes (%lld x %d, at most %lld)", B, C, MAX_PLANES);
     CredArgs a;
     a.x = x;

@@ -6,19 +6,11 @@
 // One workgroup per plane, ONE pass over HBM: the three sums are known once the ground-truth logit has been read.  16-byte loads, eight
 // in flight per thread, as softargmax_plane (glue.hip) but without its row / column bookkeeping.  Per-pixel terms are fp32; the running
 // sums, the cross-wave combine and the final logs are fp64.  The public C ABI is include/ynet_hip.h.
-#include "ynet_common.h"
-#include "sigmoid_term.h"
-#include <math.h>
+#include "map_plane.h"
 
 namespace {
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// One logit in fp32 (z and w: sigmoid_term.h, shared with temperature.hip).  With a = |z|, e = exp(-a), u = 1 + e:
+// One logit in fp32 (z and w: sigmoid_term.h, shared with the sibling kernels).  With a = |z|, e = exp(-a), u = 1 + e:
 //   w = sigmoid(z) = 1 / u (z >= 0), e / u (z < 0);   log_sigmoid(z) = zmin - l1p,  zmin = min(z, 0),  l1p = log1p(e) = log(u) + (e - (u - 1)) / u
 // (the last term restores what the rounding of 1 + e dropped).  The two parts of log_sigmoid stay apart: zmin is exact and may be large,
 // l1p <= log 2 carries the rounding -- rounded into one fp32 number their sum would lose half an ulp of |z|, which a plane of a few
@@ -60,15 +52,13 @@ __global__ __launch_bounds__(256) void map_likelihood_kernel(const LikeArgs a) {
     const int tid = threadIdx.x;
     const long long plane = blockIdx.x;
     const int n = a.H * a.W;
-    const float* __restrict__ p = a.x + (plane / a.C) * a.bs + (plane % a.C) * (long long)n;
-    // the ground-truth pixel, rounded half-even like the patch windows; read only when it lies inside the map
+    const float* __restrict__ p = plane_ptr(a.x, a.bs, a.C, n, plane);
     bool in_map = false;
     float xg = INFINITY;
     if (a.gt != nullptr) {
-        const float gx = rintf(a.gt[2 * plane]), gy = rintf(a.gt[2 * plane + 1]);
-        in_map = gx >= 0.f && gx < (float)a.W && gy >= 0.f && gy < (float)a.H;      // (false for a NaN coordinate)
-        if (in_map) xg = p[(int)gy * a.W + (int)gx];
-        else if (tid == 0) atomicExch(a.status, 1);
+        const GtPixel g = gt_pixel(a.gt, plane, p, a.H, a.W, a.status, tid);
+        in_map = g.in_map;
+        xg = g.xg;
     }
     // running sums in fp64: sum w, sum w * zmin (every product exact in fp64), sum w * l1p, sum of w over the members of the hpd region
     double sw = 0.0, shi = 0.0, slo = 0.0, sh = 0.0;
@@ -128,10 +118,9 @@ __global__ __launch_bounds__(256) void map_likelihood_kernel(const LikeArgs a) {
     __syncthreads();
     if (tid == 0) {
         const double nan = (double)__builtin_nanf("");
-        double Z = (ws[0][0] + ws[1][0]) + (ws[2][0] + ws[3][0]);
-        const double wl = (ws[0][1] + ws[1][1]) + (ws[2][1] + ws[3][1]);
-        const double hs = (ws[0][2] + ws[1][2]) + (ws[2][2] + ws[3][2]);
-        if ((wpoison[0] | wpoison[1] | wpoison[2] | wpoison[3]) != 0 || Z == 0.0) Z = nan;
+        double Z = four_wave_sum(&ws[0][0], 3);
+        const double wl = four_wave_sum(&ws[0][1], 3), hs = four_wave_sum(&ws[0][2], 3);
+        if (four_wave_poison(wpoison) || Z == 0.0) Z = nan;
         const double logz = log(Z);
         if (a.ent != nullptr) a.ent[plane] = (float)(logz - wl / Z);
         if (a.nll != nullptr) {
@@ -151,12 +140,9 @@ __global__ __launch_bounds__(256) void map_likelihood_kernel(const LikeArgs a) {
 extern "C" int ynet_map_likelihood(const float* x, long long batch_stride, const float* gt_xy, long long B, int C, int H, int W,
                                    float temperature, float* nll, float* entropy, float* hpd, int* status, void* stream) {
     YNET_REQUIRE(x != nullptr, "map_likelihood: null map");
-    YNET_REQUIRE(temperature > 0.f && temperature <= 3.0e38f && 1.f / temperature <= 3.0e38f,
-                 "map_likelihood: the temperature and its reciprocal must be positive and finite");
-    YNET_REQUIRE(B >= 1 && C >= 1 && H >= 1 && W >= 1, "map_likelihood: bad shape B=%lld C=%d %dx%d", B, C, H, W);
-    YNET_REQUIRE((long long)H * W <= (1ll << 31) - 2048, "map_likelihood: a plane of %dx%d is beyond the 32-bit pixel index", H, W);      // (i += 256 stays an int)
-    YNET_REQUIRE(batch_stride >= (long long)C * H * W, "map_likelihood: batch stride %lld below the %d planes of %dx%d of an image",
-                 batch_stride, C, H, W);
+    if (map_check_temperature("map_likelihood", temperature) || map_check_shape("map_likelihood", B, C, H, W) ||
+        map_check_pixel_index("map_likelihood", H, W) || map_check_batch_stride("map_likelihood", batch_stride, C, H, W))
+        return 1;
     YNET_REQUIRE(nll != nullptr || entropy != nullptr || hpd != nullptr, "map_likelihood: no output asked for");
     YNET_REQUIRE(gt_xy != nullptr || (nll == nullptr && hpd == nullptr), "map_likelihood: nll and hpd need the ground truth (gt_xy is null)");
     YNET_REQUIRE(gt_xy == nullptr || status != nullptr, "map_likelihood: the ground truth needs a status flag (status is null)");

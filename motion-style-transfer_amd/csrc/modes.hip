@@ -15,10 +15,9 @@
 // compares know nothing of denormal flushing -- and (key, index) travel as ONE 64-bit number whose maximum is the winner: the larger
 // key, and among equal keys the smaller index, whichever thread, wave or segment saw it.
 // Sums are fp64; every pixel belongs to a fixed thread, and the partial sums are combined in a fixed tree: two runs give the same bits.
-#include "ynet_common.h"
+#include "map_plane.h"
 #include "../../include/ynet_hip.h"
 #include <limits.h>
-#include <math.h>
 
 namespace {
 
@@ -82,7 +81,8 @@ __device__ __forceinline__ long long wave_max(long long v) {
     return llmax(llmax(lane64(v, 0), lane64(v, 16)), llmax(lane64(v, 32), lane64(v, 48)));
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
+// (not map_plane.h's wave_sum: another tree, so other bits)
+__device__ __forceinline__ double wave_sum_dpp(double v) {
     v += __longlong_as_double(dpp64<ROW_ROR + 8>(__double_as_longlong(v)));
     v += __longlong_as_double(dpp64<ROW_ROR + 4>(__double_as_longlong(v)));
     v += __longlong_as_double(dpp64<ROW_ROR + 2>(__double_as_longlong(v)));
@@ -95,6 +95,8 @@ __device__ __forceinline__ double wave_sum(double v) {
 // sigmoid(x / T) in fp32, formed as map_likelihood_kernel (likelihood.hip) forms its weight: the quotient as the product with 1 / T
 // corrected by its exact residual, e = exp(-|z|) from v_exp_f32 corrected to first order, w = 1 / (1 + e) or e / (1 + e).
 // -inf gives exactly 0, +inf exactly 1; a NaN never adds to a mass (its plane is not ranked).
+// (Not sigmoid_term.h's weight<DIVIDE>, which map_plane.h brings in beside it: this one switches on T at run time, the same bits through
+// another instruction stream.  A call without a template argument is this overload.)
 __device__ __forceinline__ float weight(float x, float inv_t, float t) {
     float z = x;
     if (t != 1.f) {
@@ -135,7 +137,7 @@ __global__ __launch_bounds__(THREADS) void map_modes_kernel(const ModesArgs a) {
     const long long plane = blockIdx.x;
     const int H = a.H, W = a.W, M = a.M;
     const int n = H * W, nseg = (n + SEG - 1) / SEG;
-    const float* __restrict__ p = a.x + (plane / a.C) * a.bs + (plane % a.C) * (long long)n;
+    const float* __restrict__ p = plane_ptr(a.x, a.bs, a.C, n, plane);
     float* xy = a.xy + plane * M * 2;
     float* logit = a.logit + plane * M;
     float* mass = MASS ? a.mass + plane * M : nullptr;
@@ -176,7 +178,7 @@ __global__ __launch_bounds__(THREADS) void map_modes_kernel(const ModesArgs a) {
             if (lane == 0 && sk < nseg) seg_best[sk] = b;
         }
     }
-    if (MASS) sw = wave_sum(sw);
+    if (MASS) sw = wave_sum_dpp(sw);
     const int any_poison = __any(poison);
     if (lane == 0) {
         wsum[wave] = sw;
@@ -246,7 +248,7 @@ __global__ __launch_bounds__(THREADS) void map_modes_kernel(const ModesArgs a) {
                 }
             }
             if (MASS) {
-                acc = wave_sum(acc);
+                acc = wave_sum_dpp(acc);
                 if (lane == 0) wsum[wave] = acc;
             }
             __syncthreads();                          // the bitmap is complete (and wbest read by everyone)
@@ -295,11 +297,10 @@ extern "C" int ynet_map_modes(const float* x, long long batch_stride, long long 
                  "map_modes: null map, xy, logit, count or status");
     YNET_REQUIRE(n_modes >= 1 && n_modes <= MAX_MODES, "map_modes: n_modes = %d, expected 1 .. %d", n_modes, MAX_MODES);
     YNET_REQUIRE(radius >= 0, "map_modes: radius = %d is negative", radius);
-    YNET_REQUIRE(B >= 1 && C >= 1 && H >= 1 && W >= 1, "map_modes: bad shape B=%lld C=%d %dx%d", B, C, H, W);
+    if (map_check_shape("map_modes", B, C, H, W)) return 1;
     YNET_REQUIRE((long long)H * W <= MAX_PIXELS, "map_modes: a plane of %dx%d is beyond the cap of %d pixels (the LDS suppression bitmap)",
                  H, W, MAX_PIXELS);
-    YNET_REQUIRE(batch_stride >= (long long)C * H * W, "map_modes: batch stride %lld below the %d planes of %dx%d of an image",
-                 batch_stride, C, H, W);
+    if (map_check_batch_stride("map_modes", batch_stride, C, H, W)) return 1;
     YNET_REQUIRE(mass == nullptr || (temperature > 0.f && temperature <= 3.0e38f && 1.f / temperature <= 3.0e38f),
                  "map_modes: with mass, the temperature and its reciprocal must be positive and finite");
     YNET_REQUIRE(B <= MAX_PLANES / C, "map_modes: more than %d planes", MAX_PLANES);

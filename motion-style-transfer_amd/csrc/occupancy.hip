@@ -16,24 +16,10 @@
 //   3. occupancy_combine_kernel     the tile partials of every (g, c) and (a, c), summed in a fixed order in fp64
 // Per-pixel terms are fp32 (sigmoid_term.h: the same z and the same w as the likelihood kernels form).  The public C ABI is
 // include/ynet_hip.h.
-#include "ynet_common.h"
-#include "sigmoid_term.h"
+#include "map_plane.h"
 #include "../../include/ynet_hip.h"
-#include <math.h>
 
 namespace {
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-template <bool DIVIDE>
-__device__ __forceinline__ float weight(float x, float inv_t, float t) {
-    const float z = tempered<DIVIDE>(x, inv_t, t);
-    return sigmoid_weight(z, sigmoid_term(z));
-}
 
 // ---- 1. the normalisers -----------------------------------------------------------------------------------------------------------------
 struct NormArgs {
@@ -53,7 +39,7 @@ __global__ __launch_bounds__(256) void occupancy_normalise_kernel(const NormArgs
     const long long plane = blockIdx.x;
     const long long row = plane / a.C;
     const int n = a.H * a.W;
-    const float* __restrict__ p = a.x + row * a.bs + (plane % a.C) * (long long)n;
+    const float* __restrict__ p = a.x + row * a.bs + (plane % a.C) * (long long)n;      // (plane_ptr, spelled out: see map_plane.h)
     double sw = 0.0;
     bool poison = false;    // (bit-wise ors below: a short-circuit || is a branch)
     auto fold1 = [&](const float v) {
@@ -109,8 +95,8 @@ __global__ __launch_bounds__(256) void occupancy_normalise_kernel(const NormArgs
     }
     __syncthreads();
     if (tid == 0) {
-        const double Z = (ws[0] + ws[1]) + (ws[2] + ws[3]);
-        const bool bad = (wpoison[0] | wpoison[1] | wpoison[2] | wpoison[3]) != 0 || Z == 0.0;
+        const double Z = four_wave_sum(ws, 1);
+        const bool bad = four_wave_poison(wpoison) || Z == 0.0;
         a.rz[plane] = bad ? __builtin_nan("") : 1.0 / Z;      // (the NaN travels: every m, D, product and partial it enters is NaN)
     }
 }
@@ -439,12 +425,9 @@ extern "C" int ynet_map_occupancy(const float* x, long long batch_stride, const 
     YNET_REQUIRE((((uintptr_t)workspace) & 7) == 0, "map_occupancy: the workspace must start on an 8-byte boundary");
     YNET_REQUIRE(status != nullptr, "map_occupancy: null status flag");
     YNET_REQUIRE(cell_ok(cell), "map_occupancy: cell = %d, expected 1, 2, 4 or %d", cell, YNET_MAP_OCCUPANCY_MAX_CELL);
-    YNET_REQUIRE(temperature > 0.f && temperature <= 3.0e38f && 1.f / temperature <= 3.0e38f,
-                 "map_occupancy: the temperature and its reciprocal must be positive and finite");
+    if (map_check_temperature("map_occupancy", temperature)) return 1;
     YNET_REQUIRE(B >= 1 && C >= 1 && H >= 1 && W >= 1 && G >= 1, "map_occupancy: bad shape B=%lld C=%d %dx%d G=%lld", B, C, H, W, G);
-    YNET_REQUIRE((long long)H * W <= (1ll << 31) - 2048, "map_occupancy: a plane of %dx%d is beyond the 32-bit pixel index", H, W);
-    YNET_REQUIRE(batch_stride >= (long long)C * H * W, "map_occupancy: batch stride %lld below the %d planes of %dx%d of an image",
-                 batch_stride, C, H, W);
+    if (map_check_pixel_index("map_occupancy", H, W) || map_check_batch_stride("map_occupancy", batch_stride, C, H, W)) return 1;
     int pwn;
     long long P, T;
     plan(H, W, cell, &pwn, &P, &T);

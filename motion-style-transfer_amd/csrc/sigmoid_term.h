@@ -1,5 +1,6 @@
-// The per-pixel fp32 arithmetic of the goal-map distribution sigmoid(x / T), shared by likelihood.hip (ynet_map_likelihood) and
-// temperature.hip (ynet_map_likelihood_sweep): one copy, so that both kernels form the same z and the same w from the same logit.
+// The per-pixel fp32 arithmetic of the goal-map distribution sigmoid(x / T), shared by the per-plane analytics kernels through
+// map_plane.h (likelihood.hip, temperature.hip, compliance.hip, credible.hip, occupancy.hip): one copy, so that every kernel forms the
+// same z and the same w from the same logit.  (modes.hip includes it through map_plane.h too, and keeps its own weight: see there.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,5 +44,12 @@ __device__ __forceinline__ SigmoidTerm sigmoid_term(float z) {
 
 // w from the parts above (apart from them, so that a caller that also wants log_sigmoid forms its terms in the order it always did)
 __device__ __forceinline__ float sigmoid_weight(float z, const SigmoidTerm s) { return (z >= 0.f) ? s.ru : s.e * s.ru; }
+
+// w = sigmoid(x / T) alone, for the kernels that take no logarithm
+template <bool DIVIDE>
+__device__ __forceinline__ float weight(float x, float inv_t, float t) {
+    const float z = tempered<DIVIDE>(x, inv_t, t);
+    return sigmoid_weight(z, sigmoid_term(z));
+}
 
 }  // namespace

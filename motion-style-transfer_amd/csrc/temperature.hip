@@ -8,18 +8,10 @@
 // block: wave-uniform values, read with compile-time indices, so they live in scalar registers.  Per-pixel terms are fp32 (sigmoid_term.h,
 // shared with likelihood.hip); the running sums, the cross-wave combine and the final logs are fp64, combined in a fixed order: two runs
 // give the same bits, and so do two equal temperatures of one call.  The public C ABI is include/ynet_hip.h.
-#include "ynet_common.h"
-#include "sigmoid_term.h"
+#include "map_plane.h"
 #include "../../include/ynet_hip.h"
-#include <math.h>
 
 namespace {
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 struct SweepArgs {
     const float* x;
@@ -48,28 +40,21 @@ __global__ __launch_bounds__(256, NT <= 16 ? 4 : NT == 24 ? 3 : 2) void map_like
     const int tid = threadIdx.x;
     const long long plane = blockIdx.x;
     const int n = a.H * a.W;
-    const float* __restrict__ p = a.x + (plane / a.C) * a.bs + (plane % a.C) * (long long)n;
-    // the ground-truth pixel, rounded half-even like the patch windows; read only when it lies inside the map
-    const float gx = rintf(a.gt[2 * plane]), gy = rintf(a.gt[2 * plane + 1]);
-    const bool in_map = gx >= 0.f && gx < (float)a.W && gy >= 0.f && gy < (float)a.H;      // (false for a NaN coordinate)
-    float xg = INFINITY;
-    if (in_map) xg = p[(int)gy * a.W + (int)gx];
-    else if (tid == 0) atomicExch(a.status, 1);
+    const float* __restrict__ p = a.x + (plane / a.C) * a.bs + (plane % a.C) * (long long)n;      // (plane_ptr, spelled out: see map_plane.h)
+    const GtPixel g = gt_pixel(a.gt, plane, p, a.H, a.W, a.status, tid);
+    const bool in_map = g.in_map;
+    const float xg = g.xg;
     // per temperature: sum w, and the sum of w over the members of the hpd region
     double sw[NT], sh[NT];
 #pragma unroll
     for (int k = 0; k < NT; ++k) sw[k] = sh[k] = 0.0;
     bool poison = false;    // a NaN logit makes the whole plane NaN  (bit-wise ors below: a short-circuit || is a branch)
-    auto weight = [](const float v, const float it, const float t) {
-        const float z = tempered<true>(v, it, t);
-        return sigmoid_weight(z, sigmoid_term(z));
-    };
     auto fold1 = [&](const float v) {
         poison = poison | (v != v);
         const bool m = v >= xg;
 #pragma unroll
         for (int k = 0; k < NT; ++k) {
-            const float w = weight(v, a.inv_t[k], a.t[k]);
+            const float w = weight<true>(v, a.inv_t[k], a.t[k]);
             sw[k] += (double)w;
             sh[k] += (double)(m ? w : 0.f);
         }
@@ -80,7 +65,7 @@ __global__ __launch_bounds__(256, NT <= 16 ? 4 : NT == 24 ? 3 : 2) void map_like
 #pragma unroll
         for (int k = 0; k < NT; ++k) {
             const float t = a.t[k], it = a.inv_t[k];
-            const float w0 = weight(v.x, it, t), w1 = weight(v.y, it, t), w2 = weight(v.z, it, t), w3 = weight(v.w, it, t);
+            const float w0 = weight<true>(v.x, it, t), w1 = weight<true>(v.y, it, t), w2 = weight<true>(v.z, it, t), w3 = weight<true>(v.w, it, t);
             sw[k] += (double)((w0 + w1) + (w2 + w3));
             // (the same four values in the same tree as sw: where every pixel is a member the two sums are equal bit for bit, and hpd == 1)
             sh[k] += (double)(((m0 ? w0 : 0.f) + (m1 ? w1 : 0.f)) + ((m2 ? w2 : 0.f) + (m3 ? w3 : 0.f)));
@@ -137,9 +122,9 @@ __global__ __launch_bounds__(256, NT <= 16 ? 4 : NT == 24 ? 3 : 2) void map_like
     }
     if (tid < a.n_temps) {
         const double nan = (double)__builtin_nanf("");
-        double Z = (ws[0][tid][0] + ws[1][tid][0]) + (ws[2][tid][0] + ws[3][tid][0]);
-        const double hs = (ws[0][tid][1] + ws[1][tid][1]) + (ws[2][tid][1] + ws[3][tid][1]);
-        if ((wpoison[0] | wpoison[1] | wpoison[2] | wpoison[3]) != 0 || Z == 0.0) Z = nan;
+        double Z = four_wave_sum(&ws[0][tid][0], 2 * NT);
+        const double hs = four_wave_sum(&ws[0][tid][1], 2 * NT);
+        if (four_wave_poison(wpoison) || Z == 0.0) Z = nan;
         const long long o = (long long)tid * a.planes + plane;
         if (a.nll != nullptr) {
             double v = nan;
@@ -166,10 +151,9 @@ extern "C" int ynet_map_likelihood_sweep(const float* x, long long batch_stride,
         YNET_REQUIRE(t > 0.f && t <= 3.0e38f && 1.f / t <= 3.0e38f,
                      "map_likelihood_sweep: temperature %d: it and its reciprocal must be positive and finite", k);
     }
-    YNET_REQUIRE(B >= 1 && C >= 1 && H >= 1 && W >= 1, "map_likelihood_sweep: bad shape B=%lld C=%d %dx%d", B, C, H, W);
-    YNET_REQUIRE((long long)H * W <= (1ll << 31) - 2048, "map_likelihood_sweep: a plane of %dx%d is beyond the 32-bit pixel index", H, W);
-    YNET_REQUIRE(batch_stride >= (long long)C * H * W, "map_likelihood_sweep: batch stride %lld below the %d planes of %dx%d of an image",
-                 batch_stride, C, H, W);
+    if (map_check_shape("map_likelihood_sweep", B, C, H, W) || map_check_pixel_index("map_likelihood_sweep", H, W) ||
+        map_check_batch_stride("map_likelihood_sweep", batch_stride, C, H, W))
+        return 1;
     YNET_REQUIRE(nll != nullptr || hpd != nullptr, "map_likelihood_sweep: no output asked for");
     YNET_REQUIRE(gt_xy != nullptr, "map_likelihood_sweep: nll and hpd need the ground truth (gt_xy is null)");
     YNET_REQUIRE(status != nullptr, "map_likelihood_sweep: the ground truth needs a status flag (status is null)");

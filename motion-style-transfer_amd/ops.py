@@ -2373,7 +2373,30 @@ def sigmoid_temp(x: torch.Tensor, channels: Sequence[int], temperature: float) -
     return y
 
 
-_patch_status = {}
+class _StatusFlag:
+    """One int32 per device that kernels raise for what only they can see; read, reported and cleared at a sync point by check()."""
+
+    def __init__(self, message: str, error=RuntimeError):
+        self.message, self.error, self._flags = message, error, {}
+
+    def on(self, dev) -> torch.Tensor:
+        st = self._flags.get(dev)
+        if st is None:
+            st = self._flags[dev] = torch.zeros(1, device=dev, dtype=torch.int32)
+        return st
+
+    def check(self, raise_error: bool = True) -> bool:
+        hit = False
+        for st in self._flags.values():
+            if int(st.item()) != 0:
+                st.zero_()
+                hit = True
+        if hit and raise_error:
+            raise self.error(self.message)
+        return hit
+
+
+_patch_status = _StatusFlag("get_patch: a window left the template (device-side coordinates)", ValueError)
 
 
 def check_patch_windows(template_shape, xy, H: int, W: int):
@@ -2458,7 +2481,7 @@ def gather_patches(template, xy, H: int, W: int) -> torch.Tensor:
         coords = torch.from_numpy(host).to(dev, non_blocking=True)
     n = coords.shape[0]
     out = torch.empty((n, H, W), device=dev, dtype=torch.float32)
-    st = _status_flag(_patch_status, dev)
+    st = _patch_status.on(dev)
     lib = _lib()
     L.check(lib.ynet_gather_patch(template.data_ptr(), SH, SW, coords.data_ptr(), out.data_ptr(), n, H, W,
                                   st.data_ptr(), _stream()), lib)
@@ -2477,7 +2500,7 @@ def _analytic_patches(t: AnalyticTemplate, xy, H: int, W: int) -> torch.Tensor:
         coords = torch.from_numpy(np.ascontiguousarray(check_patch_windows(t.shape, xy, H, W))).to(dev, non_blocking=True)
     n = coords.shape[0]
     out = torch.empty((n, H, W), device=dev, dtype=torch.float32)
-    st = _status_flag(_patch_status, dev)
+    st = _patch_status.on(dev)
     lib = _lib()
     L.check(lib.ynet_heatmap_analytic(coords.data_ptr(), out.data_ptr(), n, H, W, t.size, 0 if t.kind == "dist" else 1, t.dmax,
                                       t.blob.data_ptr() if t.blob is not None else None,
@@ -2617,14 +2640,7 @@ def kmeans2d(points: torch.Tensor, init_idx: torch.Tensor, tol: float = 1e-3, it
     return centers, status
 
 
-_sample_status = {}
-
-
-def _status_flag(store, dev):
-    st = store.get(dev)
-    if st is None:
-        st = store[dev] = torch.zeros(1, device=dev, dtype=torch.int32)
-    return st
+_sample_status = _StatusFlag("invalid multinomial distribution (a row with too few positive entries)")
 
 
 def multinomial(prob: torch.Tensor, num_samples: int, replacement: bool = False, rel_threshold=None, seed=0) -> torch.Tensor:
@@ -2638,7 +2654,7 @@ def multinomial(prob: torch.Tensor, num_samples: int, replacement: bool = False,
     if prob.stride(1) != 1:
         prob = prob.contiguous()
     out = torch.empty((rows, num_samples), device=prob.device, dtype=torch.int64)
-    st = _status_flag(_sample_status, prob.device)
+    st = _sample_status.on(prob.device)
     lib = _lib()
     if torch.is_tensor(seed):
         # the seed as a device input (one int64 element, read by the kernel): what a captured evaluation sweep passes
@@ -2675,7 +2691,7 @@ def cws_prior(sig: torch.Tensor, mean_xy: torch.Tensor, dist_xy: torch.Tensor, s
     return out_map, out_xy
 
 
-_score_status = {}
+_score_status = _StatusFlag("")      # (no message: _score_rank reads the flag in place after its own launch and words the two codes itself)
 
 
 def _score_rank(name: str, prob, waypoint_samples, trajs, resize_factor, with_rows: bool, out_row=None):
@@ -2708,7 +2724,7 @@ def _score_rank(name: str, prob, waypoint_samples, trajs, resize_factor, with_ro
         ranked_goals = torch.empty((B, K, n_wp, 2), device=dev, dtype=torch.float32)
         score = torch.empty((B, K), device=dev, dtype=torch.float32)
         order = torch.empty((B, K), device=dev, dtype=torch.int32)
-        st = _status_flag(_score_status, dev)
+        st = _score_status.on(dev)
         # x / resize_factor as torch divides a float tensor by a Python number on the device: the reciprocal taken in double, rounded to fp32, one product
         inv = float(np.float32(1.0 / float(resize_factor)))
         lib = _lib()
@@ -2770,7 +2786,7 @@ def score_rank_samples_rows(prob: torch.Tensor, waypoint_samples: torch.Tensor, 
     return _score_rank("score_rank_samples_rows", prob, waypoint_samples, trajs, resize_factor, True, out_row)
 
 
-_gather_status = {}
+_gather_status = _StatusFlag("gather_rows: an index lies outside the source")
 
 
 def gather_rows(src: torch.Tensor, idx) -> torch.Tensor:
@@ -2787,7 +2803,7 @@ def gather_rows(src: torch.Tensor, idx) -> torch.Tensor:
         raise ValueError(f"gather_rows: an index lies outside 0 .. {src.shape[0] - 1}")
     n, row_floats = rows.numel(), src[0].numel()
     dst = torch.empty((n,) + tuple(src.shape[1:]), device=src.device, dtype=torch.float32)
-    st = _status_flag(_gather_status, src.device)
+    st = _gather_status.on(src.device)
     lib = _lib()
     L.check(lib.ynet_gather_rows(src.detach().data_ptr(), src.shape[0], rows.data_ptr(), dst.data_ptr(), n, row_floats, st.data_ptr(),
                                  _stream()), lib)
@@ -2796,13 +2812,45 @@ def gather_rows(src: torch.Tensor, idx) -> torch.Tensor:
 
 def check_gather_status():
     """Raise if a gather_rows call met a device-side index outside its source (checked at a sync point)."""
-    for dev, st in _gather_status.items():
-        if int(st.item()) != 0:
-            st.zero_()
-            raise RuntimeError("gather_rows: an index lies outside the source")
+    _gather_status.check()
 
 
-_likelihood_status = {}
+# ---- the call-side checks the goal-map analytics share; every wrapper calls them in its own order, so that a call with several faults
+# ---- reports the one it always did
+def _want(want, allowed, what: str, allow_empty: bool = False):
+    want = tuple(want)
+    if (not want and not allow_empty) or len(set(want)) != len(want) or any(w not in allowed for w in want):
+        raise ValueError(f"{what}: want {want!r}: a {'' if allow_empty else 'non-empty '}selection of {allowed} is expected")
+    return want
+
+
+def _check_temperature(temperature, what: str):
+    if not (float(temperature) > 0 and np.isfinite(float(temperature))):
+        raise ValueError(f"{what}: temperature {temperature!r} must be positive and finite")
+
+
+def _host_sequence(seq, what: str, noun: str):
+    """``seq`` as NumPy can take it: a host tensor as its array, a device tensor refused."""
+    if torch.is_tensor(seq):
+        if seq.is_cuda:
+            raise TypeError(f"{what}: the {noun} are read on the host at call time; pass a host sequence, not a device tensor")
+        seq = seq.detach().numpy()
+    return seq
+
+
+def _gt_pixels(gt_xy, t: torch.Tensor, c: int, what: str) -> torch.Tensor:
+    """The ground truth [B, c, 2] of the map ``t`` as the kernels read it: contiguous fp32."""
+    _need_gpu(gt_xy, f"{what} gt_xy", dtypes=(torch.float32, torch.float64))
+    if tuple(gt_xy.shape) != (t.shape[0], c, 2):
+        raise ValueError(f"{what}: gt_xy {tuple(gt_xy.shape)} does not go with the map {tuple(t.shape)} (expected {(t.shape[0], c, 2)})")
+    return gt_xy.detach().float().contiguous()
+
+
+def _out_ptrs(out, names):
+    return {w: (out[w].data_ptr() if w in out else None) for w in names}
+
+
+_likelihood_status = _StatusFlag("map_likelihood: a ground-truth position lies outside the map (its nll and hpd are NaN)")
 LIKELIHOOD_OUTPUTS = ("nll", "entropy", "hpd")
 
 
@@ -2813,26 +2861,20 @@ def map_likelihood(x: torch.Tensor, gt_xy=None, temperature: float = 1.0, want: 
     -> dict of [B, C] device tensors, one per name in ``want``: "nll" = -log p_g (nats), "entropy" (nats), "hpd" = the mass of
     {p >= p_g}, membership decided on the raw logits.  A channel view such as x[:, 1:3] is read in place.  Not differentiable.
     A ground truth outside the map gives NaN nll / hpd for its plane and raises at the next check_likelihood_status()."""
-    want = tuple(want)
-    if not want or len(set(want)) != len(want) or any(w not in LIKELIHOOD_OUTPUTS for w in want):
-        raise ValueError(f"map_likelihood: want {want!r}: a non-empty selection of {LIKELIHOOD_OUTPUTS} is expected")
+    want = _want(want, LIKELIHOOD_OUTPUTS, "map_likelihood")
     t, c, bs = _plane_desc(x.detach() if torch.is_tensor(x) else x, "map_likelihood")
     B, _, H, W = t.shape
-    if not (float(temperature) > 0 and np.isfinite(float(temperature))):
-        raise ValueError(f"map_likelihood: temperature {temperature!r} must be positive and finite")
+    _check_temperature(temperature, "map_likelihood")
     dev = t.device
     gt = st = None
     if gt_xy is None:
         if "nll" in want or "hpd" in want:
             raise ValueError("map_likelihood: nll and hpd need the ground truth; without gt_xy ask for want=('entropy',)")
     else:
-        _need_gpu(gt_xy, "map_likelihood gt_xy", dtypes=(torch.float32, torch.float64))
-        if tuple(gt_xy.shape) != (B, c, 2):
-            raise ValueError(f"map_likelihood: gt_xy {tuple(gt_xy.shape)} does not go with the map {tuple(t.shape)} (expected {(B, c, 2)})")
-        gt = gt_xy.detach().float().contiguous()
-        st = _status_flag(_likelihood_status, dev)
+        gt = _gt_pixels(gt_xy, t, c, "map_likelihood")
+        st = _likelihood_status.on(dev)
     out = {w: torch.empty((B, c), device=dev, dtype=torch.float32) for w in want}
-    ptr = {w: (out[w].data_ptr() if w in out else None) for w in LIKELIHOOD_OUTPUTS}
+    ptr = _out_ptrs(out, LIKELIHOOD_OUTPUTS)
     lib = _lib()
     L.check(lib.ynet_map_likelihood(t.data_ptr(), bs, gt.data_ptr() if gt is not None else None, B, c, H, W, float(temperature),
                                     ptr["nll"], ptr["entropy"], ptr["hpd"], st.data_ptr() if st is not None else None, _stream()), lib)
@@ -2846,11 +2888,7 @@ SWEEP_MAX_TEMPS = 32      # YNET_SWEEP_MAX_TEMPS of include/ynet_hip.h
 def sweep_temperatures(temperatures, what: str = "map_likelihood_sweep") -> np.ndarray:
     """A host sequence of temperatures as the sweep kernel takes them: a contiguous fp32 array of 1 .. SWEEP_MAX_TEMPS positive, finite
     values (with finite reciprocals); anything else is refused."""
-    if torch.is_tensor(temperatures):
-        if temperatures.is_cuda:
-            raise TypeError(f"{what}: the temperatures are read on the host at call time; pass a host sequence, not a device tensor")
-        temperatures = temperatures.detach().numpy()
-    t64 = np.asarray(temperatures, dtype=np.float64).reshape(-1)
+    t64 = np.asarray(_host_sequence(temperatures, what, "temperatures"), dtype=np.float64).reshape(-1)
     if not 1 <= t64.size <= SWEEP_MAX_TEMPS:
         raise ValueError(f"{what}: {t64.size} temperatures, expected 1 .. {SWEEP_MAX_TEMPS}")
     with np.errstate(over="ignore", divide="ignore"):
@@ -2870,20 +2908,15 @@ def map_likelihood_sweep(x: torch.Tensor, gt_xy: torch.Tensor, temperatures, wan
     -> dict of [n_T, B, C] device tensors, one per name in ``want``: "nll" = -log p_g (nats), "hpd" = the mass of {p >= p_g}, membership
     decided on the raw logits.  A channel view such as x[:, 1:3] is read in place.  Not differentiable.  A ground truth outside the map
     gives NaN at every temperature for its plane and raises at the next check_likelihood_status()."""
-    want = tuple(want)
-    if not want or len(set(want)) != len(want) or any(w not in SWEEP_OUTPUTS for w in want):
-        raise ValueError(f"map_likelihood_sweep: want {want!r}: a non-empty selection of {SWEEP_OUTPUTS} is expected")
+    want = _want(want, SWEEP_OUTPUTS, "map_likelihood_sweep")
     temps = sweep_temperatures(temperatures)
     t, c, bs = _plane_desc(x.detach() if torch.is_tensor(x) else x, "map_likelihood_sweep")
     B, _, H, W = t.shape
     dev = t.device
-    _need_gpu(gt_xy, "map_likelihood_sweep gt_xy", dtypes=(torch.float32, torch.float64))
-    if tuple(gt_xy.shape) != (B, c, 2):
-        raise ValueError(f"map_likelihood_sweep: gt_xy {tuple(gt_xy.shape)} does not go with the map {tuple(t.shape)} (expected {(B, c, 2)})")
-    gt = gt_xy.detach().float().contiguous()
-    st = _status_flag(_likelihood_status, dev)
+    gt = _gt_pixels(gt_xy, t, c, "map_likelihood_sweep")
+    st = _likelihood_status.on(dev)
     out = {w: torch.empty((temps.size, B, c), device=dev, dtype=torch.float32) for w in want}
-    ptr = {w: (out[w].data_ptr() if w in out else None) for w in SWEEP_OUTPUTS}
+    ptr = _out_ptrs(out, SWEEP_OUTPUTS)
     lib = _lib()
     L.check(lib.ynet_map_likelihood_sweep(t.data_ptr(), bs, gt.data_ptr(), B, c, H, W, temps.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                           int(temps.size), ptr["nll"], ptr["hpd"], st.data_ptr(), _stream()), lib)
@@ -2893,14 +2926,7 @@ def map_likelihood_sweep(x: torch.Tensor, gt_xy: torch.Tensor, temperatures, wan
 def check_likelihood_status(raise_error: bool = True) -> bool:
     """Raise if a map_likelihood call met a ground truth that rounds outside its map (checked at a sync point); the flag is cleared.
     raise_error=False: report it instead (-> True if one did) -- evaluate() keeps such a plane's NaN nll / hpd and warns."""
-    hit = False
-    for dev, st in _likelihood_status.items():
-        if int(st.item()) != 0:
-            st.zero_()
-            hit = True
-    if hit and raise_error:
-        raise RuntimeError("map_likelihood: a ground-truth position lies outside the map (its nll and hpd are NaN)")
-    return hit
+    return _likelihood_status.check(raise_error)
 
 
 MAP_MAX_CLASSES = 8      # YNET_MAP_MAX_CLASSES of include/ynet_hip.h
@@ -2920,8 +2946,7 @@ def map_class_mass(x: torch.Tensor, labels: torch.Tensor, n_classes: int, temper
     K = int(n_classes)
     if not 1 <= K <= MAP_MAX_CLASSES:
         raise ValueError(f"map_class_mass: n_classes = {K}, expected 1 .. {MAP_MAX_CLASSES}")
-    if not (float(temperature) > 0 and np.isfinite(float(temperature))):
-        raise ValueError(f"map_class_mass: temperature {temperature!r} must be positive and finite")
+    _check_temperature(temperature, "map_class_mass")
     _need_gpu(labels, "map_class_mass labels", dtypes=(torch.uint8,))
     if tuple(labels.shape) not in ((H, W), (B, H, W)):
         raise ValueError(f"map_class_mass: labels {tuple(labels.shape)} do not go with the map {tuple(t.shape)} (expected {(H, W)} or {(B, H, W)})")
@@ -2939,7 +2964,7 @@ def map_class_mass(x: torch.Tensor, labels: torch.Tensor, n_classes: int, temper
     return out
 
 
-_credible_status = {}
+_credible_status = _StatusFlag("map_credible: a plane holds a NaN logit (no region: its area is -1)")
 MAP_MAX_LEVELS = 8                  # YNET_MAP_CREDIBLE_MAX_LEVELS of include/ynet_hip.h
 MAP_CREDIBLE_MAX_PIXELS = 1 << 22   # YNET_MAP_CREDIBLE_MAX_PIXELS
 CREDIBLE_OUTPUTS = ("area", "threshold", "mass")
@@ -2948,11 +2973,7 @@ CREDIBLE_OUTPUTS = ("area", "threshold", "mass")
 def credible_levels(levels, what: str = "map_credible") -> np.ndarray:
     """A host sequence of credible levels as the kernel takes them: a contiguous fp32 array of 1 .. MAP_MAX_LEVELS values inside the
     open interval (0, 1), strictly ascending after the conversion to fp32; anything else is refused."""
-    if torch.is_tensor(levels):
-        if levels.is_cuda:
-            raise TypeError(f"{what}: the levels are read on the host at call time; pass a host sequence, not a device tensor")
-        levels = levels.detach().numpy()
-    q64 = np.asarray(levels, dtype=np.float64).reshape(-1)
+    q64 = np.asarray(_host_sequence(levels, what, "levels"), dtype=np.float64).reshape(-1)
     if not 1 <= q64.size <= MAP_MAX_LEVELS:
         raise ValueError(f"{what}: {q64.size} levels, expected 1 .. {MAP_MAX_LEVELS}")
     q = np.ascontiguousarray(q64.astype(np.float32))
@@ -2975,15 +2996,14 @@ def map_credible(x: torch.Tensor, levels, temperature: float = 1.0):
     q = credible_levels(levels)
     t, c, bs = _plane_desc(x.detach() if torch.is_tensor(x) else x, "map_credible")
     B, _, H, W = t.shape
-    if not (float(temperature) > 0 and np.isfinite(float(temperature))):
-        raise ValueError(f"map_credible: temperature {temperature!r} must be positive and finite")
+    _check_temperature(temperature, "map_credible")
     if H * W > MAP_CREDIBLE_MAX_PIXELS:
         raise ValueError(f"map_credible: a plane of {H}x{W} has more than the {MAP_CREDIBLE_MAX_PIXELS} pixels the integer sums hold")
     dev = t.device
     out = {"area": torch.empty((B, c, q.size), device=dev, dtype=torch.int32),
            "threshold": torch.empty((B, c, q.size), device=dev, dtype=torch.float32),
            "mass": torch.empty((B, c, q.size), device=dev, dtype=torch.float32)}
-    st = _status_flag(_credible_status, dev)
+    st = _credible_status.on(dev)
     lib = _lib()
     L.check(lib.ynet_map_credible(t.data_ptr(), bs, B, c, H, W, q.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), int(q.size),
                                   float(temperature), out["area"].data_ptr(), out["threshold"].data_ptr(), out["mass"].data_ptr(),
@@ -2994,17 +3014,10 @@ def map_credible(x: torch.Tensor, levels, temperature: float = 1.0):
 def check_credible_status(raise_error: bool = True) -> bool:
     """Raise if a map_credible call met a plane that holds a NaN (checked at a sync point); the flag is cleared.
     raise_error=False: report it instead (-> True if one did)."""
-    hit = False
-    for dev, st in _credible_status.items():
-        if int(st.item()) != 0:
-            st.zero_()
-            hit = True
-    if hit and raise_error:
-        raise RuntimeError("map_credible: a plane holds a NaN logit (no region: its area is -1)")
-    return hit
+    return _credible_status.check(raise_error)
 
 
-_occupancy_status = {}
+_occupancy_status = _StatusFlag("map_occupancy: a plane holds a NaN logit or has no weight at all (its group is NaN at that step)")
 _occupancy_offsets = {}             # (device, the bounds' bytes) -> the bounds on the device: a repeated layout is uploaded once
 OCCUPANCY_CELLS = (1, 2, 4, 8)      # up to YNET_MAP_OCCUPANCY_MAX_CELL of include/ynet_hip.h
 OCCUPANCY_OUTPUTS = ("occupancy", "any", "conflict", "risk")
@@ -3015,10 +3028,7 @@ def occupancy_offsets(group_sizes, B: int, what: str = "map_occupancy") -> np.nd
     that together hold exactly the B rows; None is one group of all rows.  Anything else is refused."""
     if group_sizes is None:
         return np.array([0, B], dtype=np.int32)
-    if torch.is_tensor(group_sizes):
-        if group_sizes.is_cuda:
-            raise TypeError(f"{what}: the group sizes are read on the host at call time; pass a host sequence, not a device tensor")
-        group_sizes = group_sizes.detach().numpy()
+    group_sizes = _host_sequence(group_sizes, what, "group sizes")
     raw = np.asarray(group_sizes).reshape(-1)
     if raw.size < 1 or raw.dtype.kind not in "iu":
         raise ValueError(f"{what}: group_sizes must be a non-empty sequence of integers, got {group_sizes!r}")
@@ -3044,14 +3054,11 @@ def map_occupancy(x: torch.Tensor, group_sizes=None, cell: int = 1, temperature:
     One call; the map is read about twice (three times with "risk").  A channel view such as x[:, -1:] is read in place.  Not
     differentiable.  Two calls give the same bits.  A plane that holds a NaN logit, or whose weights are all 0, makes every result of
     its group at that step NaN, and the next check_occupancy_status() raises."""
-    want = tuple(want)
-    if len(set(want)) != len(want) or any(w not in OCCUPANCY_OUTPUTS for w in want):
-        raise ValueError(f"map_occupancy: want {want!r}: a selection of {OCCUPANCY_OUTPUTS} is expected")
+    want = _want(want, OCCUPANCY_OUTPUTS, "map_occupancy", allow_empty=True)
     if cell not in OCCUPANCY_CELLS:
         raise ValueError(f"map_occupancy: cell = {cell!r}, expected one of {OCCUPANCY_CELLS}")
     cell = int(cell)
-    if not (float(temperature) > 0 and np.isfinite(float(temperature))):
-        raise ValueError(f"map_occupancy: temperature {temperature!r} must be positive and finite")
+    _check_temperature(temperature, "map_occupancy")
     t, c, bs = _plane_desc(x.detach() if torch.is_tensor(x) else x, "map_occupancy")
     B, _, H, W = t.shape
     if B < 1 or c < 1 or H < 1 or W < 1:
@@ -3067,7 +3074,7 @@ def map_occupancy(x: torch.Tensor, group_sizes=None, cell: int = 1, temperature:
         out["conflict"] = torch.empty((G, c), device=dev, dtype=torch.float32)
     if "risk" in want:
         out["risk"] = torch.empty((B, c), device=dev, dtype=torch.float32)
-    ptr = {w: (out[w].data_ptr() if w in out else None) for w in OCCUPANCY_OUTPUTS}
+    ptr = _out_ptrs(out, OCCUPANCY_OUTPUTS)
     lib = _lib()
     need = lib.ynet_map_occupancy_workspace_bytes(B, c, H, W, G, cell)
     if need < 0:
@@ -3079,7 +3086,7 @@ def map_occupancy(x: torch.Tensor, group_sizes=None, cell: int = 1, temperature:
         if len(_occupancy_offsets) >= 16:
             _occupancy_offsets.clear()
         off_dev = _occupancy_offsets[key] = torch.from_numpy(offsets).to(dev)
-    st = _status_flag(_occupancy_status, dev)
+    st = _occupancy_status.on(dev)
     L.check(lib.ynet_map_occupancy(t.data_ptr(), bs, off_dev.data_ptr(), B, G, c, H, W, cell, float(temperature), ptr["occupancy"], ptr["any"],
                                    ptr["conflict"], ptr["risk"], ws.data_ptr(), st.data_ptr(), _stream()), lib)
     return out
@@ -3088,17 +3095,10 @@ def map_occupancy(x: torch.Tensor, group_sizes=None, cell: int = 1, temperature:
 def check_occupancy_status(raise_error: bool = True) -> bool:
     """Raise if a map_occupancy call met a plane that holds a NaN or whose weights are all 0 (checked at a sync point); the flag is
     cleared.  raise_error=False: report it instead (-> True if one did)."""
-    hit = False
-    for dev, st in _occupancy_status.items():
-        if int(st.item()) != 0:
-            st.zero_()
-            hit = True
-    if hit and raise_error:
-        raise RuntimeError("map_occupancy: a plane holds a NaN logit or has no weight at all (its group is NaN at that step)")
-    return hit
+    return _occupancy_status.check(raise_error)
 
 
-_modes_status = {}
+_modes_status = _StatusFlag("map_modes: a plane holds a NaN logit (it was not ranked: its count is -1)")
 MAX_MODES = 64     # ynet_map_modes takes up to the MAX_SAMPLES of the ranking kernel
 
 
@@ -3117,14 +3117,14 @@ def map_modes(x: torch.Tensor, n_modes: int, radius: int, temperature: float = 1
         raise ValueError(f"map_modes: n_modes = {M}, expected 1 .. {MAX_MODES}")
     if radius < 0:
         raise ValueError(f"map_modes: radius = {radius} is negative")
-    if want_mass and not (float(temperature) > 0 and np.isfinite(float(temperature))):
-        raise ValueError(f"map_modes: temperature {temperature!r} must be positive and finite")
+    if want_mass:
+        _check_temperature(temperature, "map_modes")
     dev = t.device
     out = {"xy": torch.empty((B, c, M, 2), device=dev, dtype=torch.float32), "logit": torch.empty((B, c, M), device=dev, dtype=torch.float32),
            "count": torch.empty((B, c), device=dev, dtype=torch.int32)}
     if want_mass:
         out["mass"] = torch.empty((B, c, M), device=dev, dtype=torch.float32)
-    st = _status_flag(_modes_status, dev)
+    st = _modes_status.on(dev)
     lib = _lib()
     L.check(lib.ynet_map_modes(t.data_ptr(), bs, B, c, H, W, M, radius, float(temperature) if want_mass else 1.0, out["xy"].data_ptr(),
                                out["logit"].data_ptr(), out["mass"].data_ptr() if want_mass else None, out["count"].data_ptr(),
@@ -3135,23 +3135,10 @@ def map_modes(x: torch.Tensor, n_modes: int, radius: int, temperature: float = 1
 def check_modes_status(raise_error: bool = True) -> bool:
     """Raise if a map_modes call met a plane that holds a NaN (checked at a sync point); the flag is cleared.
     raise_error=False: report it instead (-> True if one did) -- predict_modes names the agent itself."""
-    hit = False
-    for dev, st in _modes_status.items():
-        if int(st.item()) != 0:
-            st.zero_()
-            hit = True
-    if hit and raise_error:
-        raise RuntimeError("map_modes: a plane holds a NaN logit (it was not ranked: its count is -1)")
-    return hit
+    return _modes_status.check(raise_error)
 
 
 def check_patch_status():
     """Raise if a device-side coordinate ever left the template (checked at sync points)."""
-    for dev, st in _patch_status.items():
-        if int(st.item()) != 0:
-            st.zero_()
-            raise ValueError("get_patch: a window left the template (device-side coordinates)")
-    for dev, st in _sample_status.items():
-        if int(st.item()) != 0:
-            st.zero_()
-            raise RuntimeError("invalid multinomial distribution (a row with too few positive entries)")
+    _patch_status.check()
+    _sample_status.check()
