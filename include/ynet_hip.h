@@ -719,6 +719,47 @@ int ynet_map_occupancy(const float* x, long long batch_stride, const int* offset
                        int C, int H, int W, int cell, float temperature, float* occupancy, float* any /* or null */,
                        float* conflict /* or null */, float* risk /* or null */, void* workspace, int* status, void* stream);
 
+/* Radial scores of the goal map: the mass profile, around the ground-truth pixel, of the distribution the goals are sampled from --
+ * sigmoid(pred_goal_map / temperature), every plane normalised (utils/evaluate.py:128-131, utils/image_utils.py:110-135).  The
+ * reference's headline error, best-of-K FDE (utils/evaluate.py:268-291), is one seeded estimate of a functional of this profile: the
+ * draws are i.i.d., so with F(r) the mass closer than r, P(a draw within r) = F(r) and E[min of K distances] = integral of
+ * (1 - F(r))^K dr.  Per plane (b, c) of x [B][C][H][W] (batch stride `batch_stride` elements, so a channel slice needs no copy), with
+ * z = x / T, w = sigmoid(z), Z = sum w, g = (rint(gt_x), rint(gt_y)) (half-even; (x, y) = (column, row)), and per pixel i the INTEGER
+ * d2_i = (col_i - g.x)^2 + (row_i - g.y)^2 and its ring k_i = floor(sqrt(d2_i)), decided in integers (k^2 <= d2 < (k + 1)^2: exact):
+ *   ring [B][C][n_rings] = (sum over {k_i == k} of w_i) / Z          the share of the mass at a distance in [k, k + 1) from g
+ *   tail [B][C]          = (sum over {k_i >= n_rings} of w_i) / Z
+ *   mean [B][C]          = (sum w_i sqrt(d2_i)) / Z                    the expected distance of ONE draw, in map pixels
+ *   mean_sq [B][C]       = (sum w_i d2_i) / Z                          its second moment
+ * g need NOT lie inside the map: a ground truth up to YNET_MAP_RADIAL_GT_MARGIN pixels outside it, on either axis, still has a
+ * distance to every pixel, is scored, and raises nothing (the deliberate difference from ynet_map_likelihood, whose nll and hpd need
+ * the pixel itself).  With that margin and sides <= YNET_MAP_RADIAL_MAX_SIDE, d2 < 2^31.
+ * One launch, one workgroup per plane, the plane read from HBM once and once more through the caches.  w is fp32, formed exactly as
+ * ynet_map_likelihood forms it.  Arithmetic: ring and tail are sums of 64-bit INTEGERS, trunc(w * 2^(s - e)) with
+ * s = YNET_MAP_RADIAL_FRAC_BITS = 40 and e = floor(log2(largest w of the plane)) (ynet_map_credible's fixed point, the same code),
+ * added with integer LDS atomics and divided by the integer total of all bins: sum ring + tail == 1 up to the roundings of the
+ * stored fp32 values.  Truncation drops less than 2^(e - s) <= 2^-s * Z per pixel, so a share moves by less than n * 2^-s /
+ * (1 - n * 2^-s) < n * 2^-39 (n = H * W: 2^-21 at 512 x 512, 2^-23 at 256 x 256).  Every scaled w is below 2^(s + 1), so
+ * n <= YNET_MAP_RADIAL_MAX_PIXELS = 2^22 keeps a sum below 2^63.  mean and mean_sq are fp64 sums per thread, combined in a fixed
+ * order: the products w * sqrtf((float)d2) (the correctly rounded fp32 root; (float)d2 is exact below 2^24, which covers every
+ * ground truth inside a map whose diagonal is below 4096 pixels; beyond, it carries one more rounding of 2^-24) and w * d2 are formed inside an fp64 fma, the latter exact below d2 = 2^29.  No
+ * floating-point atomic anywhere: two runs give the same bits.  Planes that start on a 16-byte boundary and hold a multiple of 4
+ * pixels are read in 16-byte vectors, any other plane element by element (decided per plane).
+ * Rules: a NaN logit makes all four results of its plane NaN (every ring); a -inf logit adds 0; +inf is weight 1; sigmoids below
+ * fp32's normal range count as 0; Z == 0 makes all four NaN.  A ground truth that is NaN or infinite, or rounds to more than
+ * YNET_MAP_RADIAL_GT_MARGIN pixels outside the map on either axis: all four NaN for that plane and *status (device int, zero it
+ * first) becomes 1.  Any of ring / tail / mean / mean_sq may be NULL, not all four.
+ * Refused (non-zero, ynet_last_error) before any launch: null x, gt_xy or status; no output; n_rings outside
+ * 1 .. YNET_MAP_RADIAL_MAX_RINGS; temperature <= 0, not finite, or below 2.95e-39 (where 1 / T is not); B, C, H or W < 1; H or
+ * W > YNET_MAP_RADIAL_MAX_SIDE; H * W > YNET_MAP_RADIAL_MAX_PIXELS; batch_stride < C * H * W; B * C >= 2^31. */
+#define YNET_MAP_RADIAL_MAX_RINGS 1024
+#define YNET_MAP_RADIAL_FRAC_BITS 40
+#define YNET_MAP_RADIAL_MAX_PIXELS 4194304
+#define YNET_MAP_RADIAL_MAX_SIDE 16384
+#define YNET_MAP_RADIAL_GT_MARGIN 16384
+int ynet_map_radial(const float* x, long long batch_stride, const float* gt_xy, long long B, int C, int H, int W, float temperature,
+                    int n_rings, float* ring /* [B*C][n_rings] */, float* tail /* [B*C] */, float* mean /* [B*C] */,
+                    float* mean_sq /* [B*C] */, int* status, void* stream);
+
 /* ---- heat-map construction -------------------------------------------------------------------- */
 /* get_patch + torch.stack (utils/image_utils.py:40-63; utils/train_epoch.py:63-78;
  * utils/evaluate.py:112-114,250-253): out[n] = tmpl[SH/2 - ry : +H, SW/2 - rx : +W] with

@@ -20,6 +20,7 @@
 // after run, the sub-bins of a bin add up to it exactly, and the walk of pass k + 1 is certain to find its crossing inside the bin
 // pass k chose.  The comparison against q * Z is fp64 (q: the fp32 level taken to fp64).
 #include "map_plane.h"
+#include "map_fixed.h"
 #include "../../include/ynet_hip.h"
 #include <limits.h>
 
@@ -34,8 +35,6 @@ constexpr long long MAX_PLANES = (1 << 22) - 1;       // grid x block stays belo
 static_assert(MAXL <= SLOTS && MAXL <= WAVES, "one histogram slot and one walking wave per level");
 static_assert(YNET_MAP_CREDIBLE_MAX_PIXELS <= (1ll << (63 - (FRAC + 1))), "pixels x 2^41 stays below 2^63");
 
-typedef unsigned long long u64;
-
 // The order of the logits as an order of unsigned integers: the monotone key of modes.hip (-0.0 folded onto +0.0; integer compares
 // know nothing of denormal flushing), moved to unsigned so that its digits can be cut out.  -inf has key 0x007fffff.
 __device__ __forceinline__ unsigned key_of(float x) {
@@ -47,24 +46,6 @@ __device__ __forceinline__ unsigned key_of(float x) {
 __device__ __forceinline__ float logit_of(unsigned u) {
     const int k = (int)(u ^ 0x80000000u);
     return __int_as_float(k >= 0 ? k : (k ^ 0x7fffffff));
-}
-
-// w = mant * 2^(ex - 150), 0 <= mant < 2^24 (ex = 1 for a denormal)
-__device__ __forceinline__ void split(float w, unsigned& mant, int& ex) {
-    const unsigned b = __float_as_uint(w) & 0x7fffffffu;
-    const unsigned e = b >> 23;
-    mant = (b & 0x7fffffu) | (e ? 0x800000u : 0u);
-    ex = e ? (int)e : 1;
-}
-
-// trunc(w * 2^(k0 + 150)), by shifts.  k0 puts the plane's largest w into [2^40, 2^41); a w an ulp above it (the fp32 sigmoid is
-// monotone up to its last bits only) still stays far below 2^42.
-__device__ __forceinline__ u64 fixed(float w, int k0) {
-    unsigned mant;
-    int ex;
-    split(w, mant, ex);
-    const int s = ex + k0;
-    return s >= 0 ? ((u64)mant << (s > 39 ? 39 : s)) : (s > -32 ? (u64)(mant >> -s) : 0ull);
 }
 
 template <class F>
@@ -150,13 +131,7 @@ __global__ __launch_bounds__(THREADS) void map_credible_kernel(const CredArgs a)
         if (bad != 0 && tid == 0) atomicOr(a.status, 1);
         return;
     }
-    int k0;
-    {
-        unsigned mant;
-        int ex;
-        split(wmax, mant, ex);
-        k0 = FRAC - (31 - __builtin_clz(mant)) - ex;      // mant << (ex + k0) lies in [2^40, 2^41)
-    }
+    const int k0 = fixed_scale(wmax, FRAC);      // mant << (ex + k0) lies in [2^40, 2^41)
 
     // what the wave of level `wave` carries from pass to pass (uniform over the wave)
     unsigned my_prefix = 0, my_cabove = 0;

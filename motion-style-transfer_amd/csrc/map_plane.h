@@ -1,5 +1,5 @@
 // The shared base of the per-plane goal-map analytics (likelihood.hip, temperature.hip, compliance.hip, credible.hip, occupancy.hip,
-// modes.hip): one workgroup per plane (agent b, step c) of x [B, C, H, W], fp32 per-pixel terms (sigmoid_term.h), fp64 sums combined
+// modes.hip, radial.hip): one workgroup per plane (agent b, step c) of x [B, C, H, W], fp32 per-pixel terms (sigmoid_term.h), fp64 sums combined
 // in a fixed order.  A new per-plane entry starts from here; its streaming loop stays its own.
 #pragma once
 #include "ynet_common.h"
@@ -15,7 +15,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // plane = b * C + c of a tensor whose planes are dense (n floats) and whose images lie bs floats apart: a channel view is read in place.
-// (likelihood.hip and modes.hip call it.  The sweep, class-mass, credible and occupancy-normalise kernels spell the same expression out:
+// (likelihood.hip, modes.hip and radial.hip call it.  The sweep, class-mass, credible and occupancy-normalise kernels spell the same expression out:
 // through the function hipcc forms their scalar prologue arithmetic differently and renumbers scalar registers inside their loops.)
 __device__ __forceinline__ const float* plane_ptr(const float* x, long long bs, int C, int n, long long plane) {
     return x + (plane / C) * bs + (plane % C) * (long long)n;

@@ -184,6 +184,17 @@ def sharpness_report_of(df_metrics, images, resize_factor):
                             np.array([pixels[sid] for sid in df_metrics["sceneId"]], dtype=np.float64), resize_factor)
 
 
+def radial_report_of(df_metrics, return_radial, fde=None):
+    """The lines test(return_radial=...) prints per round (utils.radial.radial_report), from evaluate()'s radial_mean_goal, hit<r>_goal and
+    best_of_<K>_lower_goal / _upper_goal columns, beside the round's sampled FDE."""
+    from ..utils.radial import radial_options, radial_report
+    opt = radial_options(return_radial, "test(return_radial=...)")
+    return radial_report(opt["radii"], opt["k"], df_metrics["radial_mean_goal"].to_numpy(),
+                         df_metrics[[f"hit{r}_goal" for r in opt["radii"]]].to_numpy(),
+                         df_metrics[[f"best_of_{k}_lower_goal" for k in opt["k"]]].to_numpy(),
+                         df_metrics[[f"best_of_{k}_upper_goal" for k in opt["k"]]].to_numpy(), fde)
+
+
 class YNetTrainer:
     def __init__(self, params, device=None):
         self.params = params
@@ -309,7 +320,7 @@ class YNetTrainer:
 
     # ------------------------------------------------------------------------------------------
     def test(self, df_test, image_path, return_preds=False, return_samples=False, return_likelihood=False, return_compliance=False,
-             return_sharpness=False):
+             return_radial=False, return_sharpness=False):
         """``return_likelihood`` (not in the reference): evaluate() also scores the goal-map distribution against the ground truth
         (df_metrics columns nll, nll_goal, entropy_goal, hpd_goal) and every round prints its mean NLL and calibration error.
         ``return_compliance`` (not in the reference): evaluate() also reports where in the scene the goals go (df_metrics columns
@@ -317,15 +328,19 @@ class YNetTrainer:
         the mean sampled-goal rate and the share of ground-truth goals on the class, beside the share of the map the class covers.
         ``return_sharpness`` (not in the reference; False, True = (0.5, 0.9), or a tuple of levels): evaluate() also reports the size of
         the goal map's credible regions (df_metrics columns area<pct>_goal, inside<pct>_goal) and every round prints one line per level:
-        how often the ground-truth goal lies inside the region (calibration) beside the region's mean and median area (sharpness)."""
+        how often the ground-truth goal lies inside the region (calibration) beside the region's mean and median area (sharpness).
+        ``return_radial`` (not in the reference; False, True = {'radii': (4, 8, 16), 'k': (1, 5, 20)}, or such a dict): evaluate() also
+        reports the goal error the goal map implies with no draw (df_metrics columns radial_mean_goal, radial_rms_goal, hit<r>_goal,
+        best_of_<K>_lower_goal / _upper_goal) and every round prints, for the last step, the expected error of one draw, the bracket
+        around the expected best-of-K error beside the round's sampled FDE, and the mass within each radius."""
         return self._test(df_test, image_path, return_preds=return_preds, return_samples=return_samples,
                           return_likelihood=return_likelihood, return_compliance=return_compliance, return_sharpness=return_sharpness,
-                          **self.params)
+                          return_radial=return_radial, **self.params)
 
     def _test(self, df_test, image_path, dataset_name, resize_factor, batch_size, n_round, obs_len, pred_len,
               waypoints, n_goal, n_traj, temperature, rel_threshold, use_TTST, use_CWS, CWS_params,
               use_raw_data=False, return_preds=False, return_samples=False, network=None, swap_semantic=False,
-              return_likelihood=False, return_compliance=False, return_sharpness=False, **kwargs):
+              return_likelihood=False, return_compliance=False, return_sharpness=False, return_radial=False, **kwargs):
         test_images, test_loader, self.homo_mat = self.prepare_data(
             df_test, image_path, dataset_name, "test", obs_len, pred_len, resize_factor, use_raw_data)
         model = self.model.to(self.device)
@@ -340,7 +355,7 @@ class YNetTrainer:
                 "test", n_goal, n_traj, obs_len, batch_size, resize_factor, temperature, use_TTST, use_CWS,
                 rel_threshold, CWS_params, return_preds=return_preds, return_samples=return_samples,
                 network=network, swap_semantic=swap_semantic, dp=self.dp, return_likelihood=return_likelihood,
-                return_compliance=return_compliance, return_sharpness=return_sharpness)
+                return_compliance=return_compliance, return_sharpness=return_sharpness, return_radial=return_radial)
             list_metrics.append(df_metrics)
             list_trajs.append(trajs_dict)
             print(f"Round {e}: \nTest ADE: {test_ADE} \nTest FDE: {test_FDE}")
@@ -353,6 +368,8 @@ class YNetTrainer:
                 print(compliance_report(df_metrics, test_images))
             if return_sharpness:
                 print(sharpness_report_of(df_metrics, test_images, resize_factor))
+            if return_radial:
+                print(radial_report_of(df_metrics, return_radial, test_FDE))
             self.eval_ADE.append(test_ADE)
             self.eval_FDE.append(test_FDE)
         avg_ade = sum(self.eval_ADE) / len(self.eval_ADE)

@@ -5,6 +5,7 @@ stream.  There is no CPU path and no ATen fallback: host tensors raise.  torch i
 memory (torch.empty), streams and autograd bookkeeping only.
 """
 import ctypes
+import math
 from typing import List, Sequence
 
 import numpy as np
@@ -2927,6 +2928,53 @@ def check_likelihood_status(raise_error: bool = True) -> bool:
     """Raise if a map_likelihood call met a ground truth that rounds outside its map (checked at a sync point); the flag is cleared.
     raise_error=False: report it instead (-> True if one did) -- evaluate() keeps such a plane's NaN nll / hpd and warns."""
     return _likelihood_status.check(raise_error)
+
+
+_radial_status = _StatusFlag("map_radial: a ground-truth position is NaN, infinite or more than 16384 pixels outside the map "
+                             "(its plane is NaN)")
+RADIAL_OUTPUTS = ("ring", "tail", "mean", "mean_sq")
+RADIAL_MAX_RINGS = 1024      # YNET_MAP_RADIAL_MAX_RINGS of include/ynet_hip.h
+
+
+def radial_rings(H: int, W: int) -> int:
+    """The default ring count of map_radial: min(1024, ceil(hypot(H, W)) + 1), the smallest that leaves no tail for any ground truth
+    inside an H x W map (where the cap does not bind)."""
+    return min(RADIAL_MAX_RINGS, math.isqrt(H * H + W * W - 1) + 2)
+
+
+def map_radial(x: torch.Tensor, gt_xy: torch.Tensor, n_rings=None, temperature: float = 1.0, want: Sequence[str] = RADIAL_OUTPUTS):
+    """The radial mass profile, around the ground truth, of the distribution `sampling` draws from (ynet_map_radial;
+    utils/evaluate.py:128-131, utils/image_utils.py:110-135; what best-of-K FDE, utils/evaluate.py:268-291, estimates from a draw): per
+    plane of x [B, C, H, W], p = sigmoid(x / T) normalised to sum 1, in one launch.  gt_xy [B, C, 2] (x, y) = (column, row) device
+    coordinates, rounded half-even to a pixel g that may lie OUTSIDE the map (by up to 16384 pixels).
+    -> dict of device tensors, one per name in ``want``: "ring" [B, C, n_rings] = the mass at a distance in [k, k + 1) map pixels from
+    g (the ring decided in integers), "tail" [B, C] = the mass at n_rings pixels or more, "mean" [B, C] = the expected distance of one
+    draw, "mean_sq" [B, C] = its second moment.  ``n_rings`` None: radial_rings(H, W).  utils/radial.py turns the profile into hit
+    rates and expected best-of-K errors.  A channel view such as x[:, 1:3] is read in place.  Not differentiable.  Two calls give the
+    same bits.  A NaN logit or Z == 0 makes a plane NaN; a ground truth that is NaN, infinite or farther outside does too, and raises
+    at the next check_radial_status()."""
+    want = _want(want, RADIAL_OUTPUTS, "map_radial")
+    t, c, bs = _plane_desc(x.detach() if torch.is_tensor(x) else x, "map_radial")
+    B, _, H, W = t.shape
+    _check_temperature(temperature, "map_radial")
+    R = radial_rings(H, W) if n_rings is None else int(n_rings)
+    if not 1 <= R <= RADIAL_MAX_RINGS:
+        raise ValueError(f"map_radial: n_rings = {n_rings!r}, expected 1 .. {RADIAL_MAX_RINGS}")
+    dev = t.device
+    gt = _gt_pixels(gt_xy, t, c, "map_radial")
+    st = _radial_status.on(dev)
+    out = {w: torch.empty((B, c, R) if w == "ring" else (B, c), device=dev, dtype=torch.float32) for w in want}
+    ptr = _out_ptrs(out, RADIAL_OUTPUTS)
+    lib = _lib()
+    L.check(lib.ynet_map_radial(t.data_ptr(), bs, gt.data_ptr(), B, c, H, W, float(temperature), R, ptr["ring"], ptr["tail"], ptr["mean"],
+                                ptr["mean_sq"], st.data_ptr(), _stream()), lib)
+    return out
+
+
+def check_radial_status(raise_error: bool = True) -> bool:
+    """Raise if a map_radial call met a ground truth it could not score (checked at a sync point); the flag is cleared.
+    raise_error=False: report it instead (-> True if one did) -- evaluate() keeps such a plane's NaNs and warns."""
+    return _radial_status.check(raise_error)
 
 
 MAP_MAX_CLASSES = 8      # YNET_MAP_MAX_CLASSES of include/ynet_hip.h

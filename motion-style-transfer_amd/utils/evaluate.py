@@ -16,6 +16,7 @@ import torch
 from .. import ops
 from . import step_graph
 from .image_utils import SAMPLER, draw_seed, gather_patches, image2world, sampling, swap_pavement_terrain
+from .radial import radial_options, radial_summary
 from .sharpness import inside_regions, level_name, sharpness_levels
 
 
@@ -210,7 +211,7 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
              n_goal, n_traj, obs_len, batch_size, resize_factor=0.25, temperature=1, use_TTST=False, use_CWS=False,
              rel_thresh=0.002, CWS_params=None, return_preds=False, return_samples=False, network=None,
              swap_semantic=False, forced_samples=None, dp=None, max_effective_batch=256, forced_goals=None,
-             forced_ttst_samples=None, return_compliance=False, return_sharpness=False, return_likelihood=False):
+             forced_ttst_samples=None, return_compliance=False, return_radial=False, return_sharpness=False, return_likelihood=False):
     """utils/evaluate.py:37-315.  Extra keyword arguments (tests / data-parallel runs): ``forced_samples`` [K,B,nwp,2]
     per batch replaces every random draw, ``forced_goals`` [n_goal,B,1,2] per batch only the goal draw,
     ``forced_ttst_samples`` [10000,B,1,2] per batch the TTST draw; ``dp`` shards each batch over ranks.
@@ -233,8 +234,20 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
     last step; -1 for a plane with a NaN) and ``inside<pct>_goal`` (1.0 / 0.0: the logit at the rounded ground-truth goal is >= the
     region's threshold; NaN where it rounds outside the map) per level, <pct> = 100 q; with ``return_preds`` trajs_dict gains
     ``area_steps`` (int32), ``threshold_steps`` and ``inside_steps``, each [N, pred_len, L].  One launch per batch; the sweep takes the
-    branch ``return_preds`` takes, as for ``return_likelihood``."""
+    branch ``return_preds`` takes, as for ``return_likelihood``.
+    ``return_radial`` (False, True = {'radii': (4, 8, 16), 'k': (1, 5, 20)}, or such a dict) reports the goal error that distribution
+    implies, with no draw (ops.map_radial, utils/radial.py): from the mass profile of every step's plane
+    around its ground truth (resized pixels, as for ``return_likelihood``; a ground truth outside the map is scored too).  df_out gains,
+    for the last step, ``radial_mean_goal`` and ``radial_rms_goal`` (the expected error of ONE draw and its root mean square),
+    ``best_of_<K>_lower_goal`` / ``best_of_<K>_upper_goal`` per K (a bracket, one resized pixel wide, around the expectation of what
+    best-of-K FDE samples) -- all four in the units of the sdd FDE, resized pixels / resize_factor -- and ``hit<r>_goal`` per radius (the mass
+    closer than r RESIZED pixels to the goal); with ``return_preds`` trajs_dict gains ``radial_mean_steps``, ``radial_rms_steps``
+    [N, pred_len], ``radial_hit_steps`` [N, pred_len, n_radii], ``best_of_k_lower_steps`` and ``best_of_k_upper_steps``
+    [N, pred_len, n_k].  Only these reduced quantities are kept per batch, never the profile.  A plane that cannot be scored (a NaN
+    logit; a ground truth that is NaN or more than 16384 pixels outside the map) is NaN (one warning per call for the latter).  One
+    launch per batch; the sweep takes the branch ``return_preds`` takes, as for ``return_likelihood``."""
     sharp_levels = sharpness_levels(return_sharpness)      # (a bad level raises before anything runs)
+    radial = radial_options(return_radial)
     model.eval()
     waypoints = list(waypoints)
     n_wp = len(waypoints)
@@ -257,6 +270,9 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                                  f"{MAX_CLASSES} planes are told apart")
 
     sharp_lists = {k: [] for k in ("area", "threshold", "inside")} if sharp_levels is not None else None
+    RADIAL_KEYS = ("mean", "rms", "hit", "best_of_k_lower", "best_of_k_upper")
+    rad_lists = {k: [] for k in RADIAL_KEYS} if radial is not None else None
+    rad_warned = False
 
     with torch.no_grad():
         # Every packed filter is (re)written HERE, on the caller's stream: the K-sample passes below run the trajectory decoder on two
@@ -268,8 +284,10 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
             ops.check_likelihood_status()      # a report left pending by an earlier ops.map_likelihood call of the caller's is raised, not swallowed below
         if sharp_levels is not None:
             ops.check_credible_status()
+        if radial is not None:
+            ops.check_radial_status()
         plain = (forced_samples is None and forced_goals is None and not use_TTST and not use_CWS and not return_preds
-                 and not return_samples and dataset_name != "eth" and not return_likelihood and not return_compliance and sharp_levels is None)
+                 and not return_samples and dataset_name != "eth" and not return_likelihood and not return_compliance and sharp_levels is None and radial is None)
         sa = getattr(model, "softargmax_", None)
         hooked = sa is not None and (sa._forward_hooks or sa._forward_pre_hooks)
         graphs = None
@@ -348,6 +366,12 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                             sharp = ops.map_credible(pred_goal_map, sharp_levels, temperature)
                             sharp = {"area": sharp["area"], "threshold": sharp["threshold"],
                                      "inside": inside_regions(pred_goal_map, gt_future, sharp["threshold"])}
+                        if radial is not None:      # every step's profile around its ground truth: one launch, reduced at once
+                            n_rings = min(ops.RADIAL_MAX_RINGS, max(ops.radial_rings(H, W), max(radial["radii"])))
+                            rad = radial_summary(ops.map_radial(pred_goal_map, gt_future, n_rings, temperature), gt_future, H, W,
+                                                 radial["radii"], radial["k"])
+                            for k in ("mean", "rms", "best_of_k_lower", "best_of_k_upper"):      # the units of _best_of_k
+                                rad[k] = rad[k] / resize_factor
 
                         if forced_samples is not None:
                             waypoint_samples = forced_samples[b][:, lo:lo + n_local].to(device)
@@ -391,6 +415,11 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                             empty = (0, trajectory.shape[1] - obs_len, len(sharp_levels))
                             sharp = {"area": torch.zeros(empty, device=device, dtype=torch.int32), "threshold": torch.zeros(empty, device=device),
                                      "inside": torch.zeros(empty, device=device)}
+                        if radial is not None:
+                            steps_ = trajectory.shape[1] - obs_len
+                            tails = {"mean": (), "rms": (), "hit": (len(radial["radii"]),), "best_of_k_lower": (len(radial["k"]),),
+                                     "best_of_k_upper": (len(radial["k"]),)}
+                            rad = {k: torch.zeros((0, steps_) + tails[k], device=device, dtype=torch.float64) for k in RADIAL_KEYS}
                     if dp is not None:
                         sizes = dp.shard_sizes(n_global)
                         ade, fde = dp.gather_rows(ade, sizes), dp.gather_rows(fde, sizes)
@@ -400,6 +429,8 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                             comp = {k: dp.gather_rows(v, sizes) for k, v in comp.items()}
                         if sharp_levels is not None:
                             sharp = {k: dp.gather_rows(v, sizes) for k, v in sharp.items()}
+                        if radial is not None:
+                            rad = {k: dp.gather_rows(v, sizes) for k, v in rad.items()}
                     ade_list.append(ade.cpu().numpy())
                     fde_list.append(fde.cpu().numpy())
                     if return_compliance:
@@ -409,6 +440,14 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                         for k, v in sharp.items():
                             sharp_lists[k].append(v.cpu().numpy())
                         ops.check_credible_status()      # (synchronised by the copies above: a NaN logit in a goal map raises here)
+                    if radial is not None:
+                        for k, v in rad.items():
+                            rad_lists[k].append(v.cpu().numpy())
+                        if ops.check_radial_status(raise_error=False) and not rad_warned:
+                            import warnings
+                            rad_warned = True
+                            warnings.warn("evaluate(return_radial=...): a ground-truth position is NaN or more than 16384 pixels outside the "
+                                          "map; its radial scores are NaN (ADE / FDE are unaffected)")
                     if return_likelihood:
                         for k, v in like.items():
                             like_lists[k].append(v.cpu().numpy())
@@ -450,9 +489,21 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
         for l, q in enumerate(sharp_levels):
             df_out[f"area{level_name(q)}_goal"] = sharp_steps["area"][:, -1, l]
             df_out[f"inside{level_name(q)}_goal"] = sharp_steps["inside"][:, -1, l]
+    if radial is not None:
+        rad_steps = {k: np.concatenate(v, axis=0) for k, v in rad_lists.items()}      # [N, pred_len] / [N, pred_len, n] each
+        df_out["radial_mean_goal"] = rad_steps["mean"][:, -1]
+        df_out["radial_rms_goal"] = rad_steps["rms"][:, -1]
+        for j, r in enumerate(radial["radii"]):
+            df_out[f"hit{r}_goal"] = rad_steps["hit"][:, -1, j]
+        for j, k in enumerate(radial["k"]):
+            df_out[f"best_of_{k}_lower_goal"] = rad_steps["best_of_k_lower"][:, -1, j]
+            df_out[f"best_of_{k}_upper_goal"] = rad_steps["best_of_k_upper"][:, -1, j]
     if return_preds:
         for key, value in trajs_dict.items():
             trajs_dict[key] = np.concatenate(value, axis=0)
+        if radial is not None:
+            for k, v in rad_steps.items():
+                trajs_dict[("radial_" + k if k in ("mean", "rms", "hit") else k) + "_steps"] = v
         if sharp_levels is not None:
             for k, v in sharp_steps.items():
                 trajs_dict[k + "_steps"] = v

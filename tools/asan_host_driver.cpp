@@ -358,6 +358,23 @@ int main() {
             return 1;
         }
     }
+    {   // radial scores: the refusals (the ground truth is device data: the host never reads it)
+        EXPECT_REJECT(ynet_map_radial(nullptr, 16, cfp, 1, 1, 4, 4, 1.f, 5, fp, fp, fp, fp, &status, nullptr));                       // no map
+        EXPECT_REJECT(ynet_map_radial(cfp, 16, nullptr, 1, 1, 4, 4, 1.f, 5, fp, fp, fp, fp, &status, nullptr));                       // no ground truth
+        EXPECT_REJECT(ynet_map_radial(cfp, 16, cfp, 1, 1, 4, 4, 1.f, 5, nullptr, nullptr, nullptr, nullptr, &status, nullptr));       // no output
+        EXPECT_REJECT(ynet_map_radial(cfp, 16, cfp, 1, 1, 4, 4, 1.f, 5, fp, fp, fp, fp, nullptr, nullptr));                           // no status flag
+        EXPECT_REJECT(ynet_map_radial(cfp, 16, cfp, 1, 1, 4, 4, 1.f, 0, fp, fp, fp, fp, &status, nullptr));                           // n_rings outside 1 .. 1024
+        EXPECT_REJECT(ynet_map_radial(cfp, 16, cfp, 1, 1, 4, 4, 1.f, YNET_MAP_RADIAL_MAX_RINGS + 1, fp, fp, fp, fp, &status, nullptr));
+        EXPECT_REJECT(ynet_map_radial(cfp, 16, cfp, 1, 1, 4, 4, 0.f, 5, fp, fp, fp, fp, &status, nullptr));                           // temperature 0
+        EXPECT_REJECT(ynet_map_radial(cfp, 16, cfp, 1, 1, 4, 4, 0.f / 0.f, 5, fp, fp, fp, fp, &status, nullptr));                     // not finite
+        EXPECT_REJECT(ynet_map_radial(cfp, 16, cfp, 1, 1, 4, 4, 1e-39f, 5, fp, fp, fp, fp, &status, nullptr));                        // a denormal: 1 / T overflows
+        EXPECT_REJECT(ynet_map_radial(cfp, 16, cfp, 0, 1, 4, 4, 1.f, 5, fp, fp, fp, fp, &status, nullptr));                           // B, C, H, W < 1
+        EXPECT_REJECT(ynet_map_radial(cfp, 16, cfp, 1, 1, 4, 0, 1.f, 5, fp, fp, fp, fp, &status, nullptr));
+        EXPECT_REJECT(ynet_map_radial(cfp, 1ll << 20, cfp, 1, 1, YNET_MAP_RADIAL_MAX_SIDE + 1, 1, 1.f, 5, fp, fp, fp, fp, &status, nullptr));   // a side above 16384
+        EXPECT_REJECT(ynet_map_radial(cfp, 1ll << 23, cfp, 1, 1, 2048, 2049, 1.f, 5, fp, fp, fp, fp, &status, nullptr));              // above the pixel cap
+        EXPECT_REJECT(ynet_map_radial(cfp, 31, cfp, 2, 2, 4, 4, 1.f, 5, fp, fp, fp, fp, &status, nullptr));                           // batch stride below the image
+        EXPECT_REJECT(ynet_map_radial(cfp, 4, cfp, 1ll << 29, 4, 1, 1, 1.f, 5, fp, fp, fp, fp, &status, nullptr));                    // 2^31 planes
+    }
     {   // the sweep reads its temperatures on the host: exactly n_temps of them (a heap array of that length, so a read past it is seen)
         float* t32 = new float[YNET_SWEEP_MAX_TEMPS];
         float* t3 = new float[3];
