@@ -16,8 +16,7 @@ import torch
 from .. import ops
 from . import step_graph
 from .image_utils import SAMPLER, draw_seed, gather_patches, image2world, sampling, swap_pavement_terrain
-from .radial import radial_options, radial_summary
-from .sharpness import inside_regions, level_name, sharpness_levels
+from .scores import ComplianceScore, LikelihoodScore, RadialScore, SharpnessScore
 
 
 # YNET_SWEEP_STREAMS=0: the K-sample decoder passes of a batch run back to back on one stream
@@ -215,39 +214,15 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
     """utils/evaluate.py:37-315.  Extra keyword arguments (tests / data-parallel runs): ``forced_samples`` [K,B,nwp,2]
     per batch replaces every random draw, ``forced_goals`` [n_goal,B,1,2] per batch only the goal draw,
     ``forced_ttst_samples`` [10000,B,1,2] per batch the TTST draw; ``dp`` shards each batch over ranks.
-    ``return_likelihood`` scores the goal decoder's distribution itself -- sigmoid(pred_goal_map / T), every plane normalised, what
-    `sampling` draws from -- against the ground truth, with no draw (ops.map_likelihood): df_out gains the
-    columns ``nll`` (mean over the pred_len steps, nats), ``nll_goal``, ``entropy_goal`` and ``hpd_goal`` (last step), and with
-    ``return_preds`` trajs_dict gains ``nll_steps``, ``entropy_steps`` and ``hpd_steps`` [N, pred_len].  A step whose ground truth
-    lies outside the map has NaN nll / hpd (one warning per call).  The sweep then takes the
-    branch ``return_preds`` takes (same launches and draws otherwise; the captured sweep is neither used nor touched).
-    ``return_compliance`` connects that distribution to the scene (ops.map_class_mass).  The classes are
-    utils.compliance.scene_labels(val_images[scene_id]) -- the world's classes, taken before ``swap_semantic`` and the scene
-    embedding, K = the number of planes (a scene with more than 8 raises before the sweep starts).  df_out gains ``goal_mass_<k>``
-    (the share of the last step's distribution on class k), ``gt_goal_class`` (the class of the ground-truth goal pixel, -1
-    outside the map) and ``sample_goal_rate_<k>`` (the fraction of the sampled goals on class k); with ``return_preds``
-    trajs_dict gains ``class_mass_steps`` [N, pred_len, K].  One launch per batch; the sweep takes the branch ``return_preds``
-    takes, as for ``return_likelihood``.
-    ``return_sharpness`` (False, True = (0.5, 0.9), or a tuple of 1 .. 8 ascending levels in (0, 1)) reports how LARGE the credible
-    regions of that distribution are, where ``hpd`` says how well calibrated (ops.map_credible): per level q
-    the smallest set of whole logit plateaus that holds q of the mass.  df_out gains ``area<pct>_goal`` (pixels of the resized map,
-    last step; -1 for a plane with a NaN) and ``inside<pct>_goal`` (1.0 / 0.0: the logit at the rounded ground-truth goal is >= the
-    region's threshold; NaN where it rounds outside the map) per level, <pct> = 100 q; with ``return_preds`` trajs_dict gains
-    ``area_steps`` (int32), ``threshold_steps`` and ``inside_steps``, each [N, pred_len, L].  One launch per batch; the sweep takes the
-    branch ``return_preds`` takes, as for ``return_likelihood``.
-    ``return_radial`` (False, True = {'radii': (4, 8, 16), 'k': (1, 5, 20)}, or such a dict) reports the goal error that distribution
-    implies, with no draw (ops.map_radial, utils/radial.py): from the mass profile of every step's plane
-    around its ground truth (resized pixels, as for ``return_likelihood``; a ground truth outside the map is scored too).  df_out gains,
-    for the last step, ``radial_mean_goal`` and ``radial_rms_goal`` (the expected error of ONE draw and its root mean square),
-    ``best_of_<K>_lower_goal`` / ``best_of_<K>_upper_goal`` per K (a bracket, one resized pixel wide, around the expectation of what
-    best-of-K FDE samples) -- all four in the units of the sdd FDE, resized pixels / resize_factor -- and ``hit<r>_goal`` per radius (the mass
-    closer than r RESIZED pixels to the goal); with ``return_preds`` trajs_dict gains ``radial_mean_steps``, ``radial_rms_steps``
-    [N, pred_len], ``radial_hit_steps`` [N, pred_len, n_radii], ``best_of_k_lower_steps`` and ``best_of_k_upper_steps``
-    [N, pred_len, n_k].  Only these reduced quantities are kept per batch, never the profile.  A plane that cannot be scored (a NaN
-    logit; a ground truth that is NaN or more than 16384 pixels outside the map) is NaN (one warning per call for the latter).  One
-    launch per batch; the sweep takes the branch ``return_preds`` takes, as for ``return_likelihood``."""
-    sharp_levels = sharpness_levels(return_sharpness)      # (a bad level raises before anything runs)
-    radial = radial_options(return_radial)
+    Each of these adds one score of the goal decoder's distribution to df_out and, with ``return_preds``, to trajs_dict (utils/scores.py):
+    ``return_likelihood``  nll, entropy and hpd against the ground truth: LikelihoodScore
+    ``return_compliance``  the mass on every semantic class of the scene: ComplianceScore
+    ``return_sharpness``   the size of the credible regions at given levels: SharpnessScore
+    ``return_radial``      the goal error the distribution implies, hit rates and expected best-of-K: RadialScore"""
+    # in the order of df_out's columns (a bad flag value raises here, before anything runs)
+    scorers = [s for s in (LikelihoodScore(return_likelihood), ComplianceScore(return_compliance), SharpnessScore(return_sharpness),
+                           RadialScore(return_radial)) if s.on]
+    collecting = sorted(scorers, key=lambda s: s.collect_rank)      # the order of their per-batch status checks
     model.eval()
     waypoints = list(waypoints)
     n_wp = len(waypoints)
@@ -258,21 +233,6 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
         trajs_dict = {k: [] for k in keys}
     else:
         trajs_dict = None
-    like_lists = {k: [] for k in ops.LIKELIHOOD_OUTPUTS} if return_likelihood else None
-    like_warned = False
-    comp_lists = {k: [] for k in ("mass", "gt_class", "rate")} if return_compliance else None
-    scene_label_maps = {}      # scene id -> (labels [H, W] uint8 on the device, K)
-    if return_compliance:
-        from .compliance import MAX_CLASSES, point_classes, class_rates, scene_labels
-        for sid, im in val_images.items():      # (before the sweep starts, not at the first batch of the offending scene)
-            if im.dim() == 3 and im.shape[0] > MAX_CLASSES:
-                raise ValueError(f"evaluate(return_compliance=True): scene {sid} has {im.shape[0]} planes; the classes of at most "
-                                 f"{MAX_CLASSES} planes are told apart")
-
-    sharp_lists = {k: [] for k in ("area", "threshold", "inside")} if sharp_levels is not None else None
-    RADIAL_KEYS = ("mean", "rms", "hit", "best_of_k_lower", "best_of_k_upper")
-    rad_lists = {k: [] for k in RADIAL_KEYS} if radial is not None else None
-    rad_warned = False
 
     with torch.no_grad():
         # Every packed filter is (re)written HERE, on the caller's stream: the K-sample passes below run the trajectory decoder on two
@@ -280,14 +240,10 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
         # versions: in place, into the layer's persistent buffers) would be read by the other stream's cache hit with no
         # dependency on the pack kernel.  The side streams wait for this stream before their first launch.
         ops.refresh_filters(model)
-        if return_likelihood:
-            ops.check_likelihood_status()      # a report left pending by an earlier ops.map_likelihood call of the caller's is raised, not swallowed below
-        if sharp_levels is not None:
-            ops.check_credible_status()
-        if radial is not None:
-            ops.check_radial_status()
+        for s in scorers:      # a report left pending by an earlier ops.map_* call of the caller's is raised, not swallowed below
+            s.start(val_images)
         plain = (forced_samples is None and forced_goals is None and not use_TTST and not use_CWS and not return_preds
-                 and not return_samples and dataset_name != "eth" and not return_likelihood and not return_compliance and sharp_levels is None and radial is None)
+                 and not return_samples and dataset_name != "eth" and not scorers)
         sa = getattr(model, "softargmax_", None)
         hooked = sa is not None and (sa._forward_hooks or sa._forward_pre_hooks)
         graphs = None
@@ -300,8 +256,8 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
         try:
             for trajectory, df_batch, scene_id in val_loader:
                 scene_image = model.segmentation(val_images[scene_id].to(device).unsqueeze(0))
-                if return_compliance and scene_id not in scene_label_maps:      # once per scene, from the planes as prepare_data left them
-                    scene_label_maps[scene_id] = (scene_labels(val_images[scene_id].to(device)), val_images[scene_id].shape[0])
+                for s in scorers:      # the planes as prepare_data left them
+                    s.scene(scene_id, val_images[scene_id], device)
                 scene_image = model.adapt_semantic(scene_image)
                 meta_ids = df_batch[0].metaId.unique()
                 n_data = trajectory.shape[0]
@@ -356,22 +312,8 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                         gt_future = batch[:, obs_len:].to(device)
                         features, pred_goal_map, wp_sigmoid = _goal_maps(model, model.pred_features, scene_image, batch[:, :obs_len],
                                                                          input_template, waypoints, obs_len, temperature, network)
-                        if return_likelihood:      # every step's plane against its ground truth, in resized pixels: one launch
-                            like = ops.map_likelihood(pred_goal_map, gt_future, temperature)
-                        if return_compliance:      # every step's plane against the scene's label map: one launch
-                            labels, n_cls = scene_label_maps[scene_id]
-                            comp = {"mass": ops.map_class_mass(pred_goal_map, labels, n_cls, temperature),
-                                    "gt_class": point_classes(gt_future[:, -1], labels)}
-                        if sharp_levels is not None:      # every step's plane at every level: one launch
-                            sharp = ops.map_credible(pred_goal_map, sharp_levels, temperature)
-                            sharp = {"area": sharp["area"], "threshold": sharp["threshold"],
-                                     "inside": inside_regions(pred_goal_map, gt_future, sharp["threshold"])}
-                        if radial is not None:      # every step's profile around its ground truth: one launch, reduced at once
-                            n_rings = min(ops.RADIAL_MAX_RINGS, max(ops.radial_rings(H, W), max(radial["radii"])))
-                            rad = radial_summary(ops.map_radial(pred_goal_map, gt_future, n_rings, temperature), gt_future, H, W,
-                                                 radial["radii"], radial["k"])
-                            for k in ("mean", "rms", "best_of_k_lower", "best_of_k_upper"):      # the units of _best_of_k
-                                rad[k] = rad[k] / resize_factor
+                        # every step's plane against its ground truth (resized pixels) or the scene: one launch per score
+                        scores = {s: s.score(pred_goal_map, gt_future, temperature, H, W, resize_factor, scene_id) for s in scorers}
 
                         if forced_samples is not None:
                             waypoint_samples = forced_samples[b][:, lo:lo + n_local].to(device)
@@ -382,8 +324,8 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                                                                use_TTST, use_CWS, rel_thresh, CWS_params, mine(forced_goals),
                                                                mine(forced_ttst_samples))
 
-                        if return_compliance:      # the goals as drawn, in the map's pixels (before ETH's world coordinates)
-                            comp["rate"] = class_rates(point_classes(waypoint_samples[:, :, -1], labels), n_cls, dim=0).t().contiguous()
+                        for s in scorers:      # the goals as drawn, in the map's pixels (before ETH's world coordinates)
+                            s.after_draw(scores[s], waypoint_samples, scene_id)
                         if return_samples:
                             trajs_dict["goal_map"].append(pred_goal_map.cpu().numpy())
                             trajs_dict["goal_sigmoid_map"].append(model.sigmoid(pred_goal_map / temperature).cpu().numpy())
@@ -404,58 +346,15 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
                                 (trajs_samples[best, torch.arange(trajs_samples.shape[1], device=device)] / resize_factor).cpu().numpy())
                     else:
                         ade = fde = torch.zeros(0, device=device)
-                        if return_likelihood:
-                            like = {k: torch.zeros((0, trajectory.shape[1] - obs_len), device=device) for k in ops.LIKELIHOOD_OUTPUTS}
-                        if return_compliance:
-                            n_cls = scene_label_maps[scene_id][1]
-                            comp = {"mass": torch.zeros((0, trajectory.shape[1] - obs_len, n_cls), device=device),
-                                    "gt_class": torch.zeros(0, device=device, dtype=torch.int64),
-                                    "rate": torch.zeros((0, n_cls), device=device, dtype=torch.float64)}
-                        if sharp_levels is not None:
-                            empty = (0, trajectory.shape[1] - obs_len, len(sharp_levels))
-                            sharp = {"area": torch.zeros(empty, device=device, dtype=torch.int32), "threshold": torch.zeros(empty, device=device),
-                                     "inside": torch.zeros(empty, device=device)}
-                        if radial is not None:
-                            steps_ = trajectory.shape[1] - obs_len
-                            tails = {"mean": (), "rms": (), "hit": (len(radial["radii"]),), "best_of_k_lower": (len(radial["k"]),),
-                                     "best_of_k_upper": (len(radial["k"]),)}
-                            rad = {k: torch.zeros((0, steps_) + tails[k], device=device, dtype=torch.float64) for k in RADIAL_KEYS}
+                        scores = {s: s.empty(trajectory.shape[1] - obs_len, device, scene_id) for s in scorers}
                     if dp is not None:
                         sizes = dp.shard_sizes(n_global)
                         ade, fde = dp.gather_rows(ade, sizes), dp.gather_rows(fde, sizes)
-                        if return_likelihood:
-                            like = {k: dp.gather_rows(v, sizes) for k, v in like.items()}
-                        if return_compliance:
-                            comp = {k: dp.gather_rows(v, sizes) for k, v in comp.items()}
-                        if sharp_levels is not None:
-                            sharp = {k: dp.gather_rows(v, sizes) for k, v in sharp.items()}
-                        if radial is not None:
-                            rad = {k: dp.gather_rows(v, sizes) for k, v in rad.items()}
+                        scores = {s: s.gather(scores[s], dp, sizes) for s in scorers}
                     ade_list.append(ade.cpu().numpy())
                     fde_list.append(fde.cpu().numpy())
-                    if return_compliance:
-                        for k, v in comp.items():
-                            comp_lists[k].append(v.cpu().numpy())
-                    if sharp_levels is not None:
-                        for k, v in sharp.items():
-                            sharp_lists[k].append(v.cpu().numpy())
-                        ops.check_credible_status()      # (synchronised by the copies above: a NaN logit in a goal map raises here)
-                    if radial is not None:
-                        for k, v in rad.items():
-                            rad_lists[k].append(v.cpu().numpy())
-                        if ops.check_radial_status(raise_error=False) and not rad_warned:
-                            import warnings
-                            rad_warned = True
-                            warnings.warn("evaluate(return_radial=...): a ground-truth position is NaN or more than 16384 pixels outside the "
-                                          "map; its radial scores are NaN (ADE / FDE are unaffected)")
-                    if return_likelihood:
-                        for k, v in like.items():
-                            like_lists[k].append(v.cpu().numpy())
-                        if ops.check_likelihood_status(raise_error=False) and not like_warned:
-                            import warnings
-                            like_warned = True
-                            warnings.warn("evaluate(return_likelihood=True): a ground-truth position lies outside the map; its nll and hpd "
-                                          "are NaN (ADE / FDE are unaffected; utils.likelihood.calibration_curve leaves NaN entries out)")
+                    for s in collecting:      # (synchronised by its copies: sharpness raises, radial and likelihood warn once per call)
+                        s.collect(scores[s])
                     ops.check_patch_status()      # (the batch is synchronised by the copies above: a window that left the template raises here)
                 meta_id_list.append(meta_ids)
                 scene_id_list.append([scene_id] * n_data)
@@ -466,52 +365,13 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
     val_ade_arr, val_fde_arr = np.concatenate(ade_list), np.concatenate(fde_list)
     df_out = pd.DataFrame({"metaId": np.concatenate(meta_id_list), "sceneId": sum(scene_id_list, []),
                            "ade": val_ade_arr, "fde": val_fde_arr})
-    if return_likelihood:
-        steps = {k: np.concatenate(v, axis=0) for k, v in like_lists.items()}      # [N, pred_len] each
-        df_out["nll"] = steps["nll"].mean(axis=1)
-        df_out["nll_goal"] = steps["nll"][:, -1]
-        df_out["entropy_goal"] = steps["entropy"][:, -1]
-        df_out["hpd_goal"] = steps["hpd"][:, -1]
-    if return_compliance:
-        widths = {m.shape[-1] for m in comp_lists["mass"]}
-        if len(widths) != 1:
-            raise ValueError(f"evaluate(return_compliance=True): the scenes differ in their number of planes ({sorted(widths)}); "
-                             f"one table needs one set of classes")
-        mass_steps = np.concatenate(comp_lists["mass"], axis=0)      # [N, pred_len, K]
-        rates = np.concatenate(comp_lists["rate"], axis=0)
-        for k in range(mass_steps.shape[-1]):
-            df_out[f"goal_mass_{k}"] = mass_steps[:, -1, k]
-        df_out["gt_goal_class"] = np.concatenate(comp_lists["gt_class"], axis=0)
-        for k in range(rates.shape[-1]):
-            df_out[f"sample_goal_rate_{k}"] = rates[:, k]
-    if sharp_levels is not None:
-        sharp_steps = {k: np.concatenate(v, axis=0) for k, v in sharp_lists.items()}      # [N, pred_len, L] each
-        for l, q in enumerate(sharp_levels):
-            df_out[f"area{level_name(q)}_goal"] = sharp_steps["area"][:, -1, l]
-            df_out[f"inside{level_name(q)}_goal"] = sharp_steps["inside"][:, -1, l]
-    if radial is not None:
-        rad_steps = {k: np.concatenate(v, axis=0) for k, v in rad_lists.items()}      # [N, pred_len] / [N, pred_len, n] each
-        df_out["radial_mean_goal"] = rad_steps["mean"][:, -1]
-        df_out["radial_rms_goal"] = rad_steps["rms"][:, -1]
-        for j, r in enumerate(radial["radii"]):
-            df_out[f"hit{r}_goal"] = rad_steps["hit"][:, -1, j]
-        for j, k in enumerate(radial["k"]):
-            df_out[f"best_of_{k}_lower_goal"] = rad_steps["best_of_k_lower"][:, -1, j]
-            df_out[f"best_of_{k}_upper_goal"] = rad_steps["best_of_k_upper"][:, -1, j]
+    for s in scorers:
+        s.columns(df_out)
     if return_preds:
         for key, value in trajs_dict.items():
             trajs_dict[key] = np.concatenate(value, axis=0)
-        if radial is not None:
-            for k, v in rad_steps.items():
-                trajs_dict[("radial_" + k if k in ("mean", "rms", "hit") else k) + "_steps"] = v
-        if sharp_levels is not None:
-            for k, v in sharp_steps.items():
-                trajs_dict[k + "_steps"] = v
-        if return_compliance:
-            trajs_dict["class_mass_steps"] = mass_steps
-        if return_likelihood:
-            for k, v in steps.items():
-                trajs_dict[k + "_steps"] = v
+        for s in reversed(scorers):
+            s.steps(trajs_dict)
         trajs_dict["metaId"] = df_out["metaId"].to_numpy()
         trajs_dict["sceneId"] = list(df_out["sceneId"])
     return val_ade_arr.mean(), val_fde_arr.mean(), df_out, trajs_dict
