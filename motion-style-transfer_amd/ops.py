@@ -369,11 +369,19 @@ def _wino_eval_gated(srcs, H, W):
 
 
 def _count_launches(n, slice_form=False):
-    """wino_stats for n Winograd launches.  (conv2d_auto_raw and upconv_dgrad_raw keep their own bump, as they keep their own workspace lookup and filter entry:
-    both functions are left as they were until their cache is keyed by ynet_conv2d_auto_cache_layout.)"""
+    """wino_stats for n Winograd launches."""
     wino_stats["launches"] += n
     if slice_form:
         wino_stats["launches16"] = wino_stats.get("launches16", 0) + n
+
+
+def _workspace(device, floats):
+    """The implicit-GEMM kernels' scratch of at least `floats` floats: grow-only, one per (device, current stream) -- stream-ordered reuse."""
+    key = (device, torch.cuda.current_stream().cuda_stream)
+    ws = _conv_ws.get(key)
+    if ws is None or ws.numel() < floats:
+        ws = _conv_ws[key] = torch.empty(floats, device=device, dtype=torch.float32)
+    return ws
 
 
 def winograd_filter(wp: torch.Tensor, cin: int, cout: int, col0: int = 0, cols_total: int = None) -> torch.Tensor:
@@ -571,12 +579,9 @@ def _auto_flags(wino):
     return flags
 
 
-def conv2d_auto_raw(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=None, pooled=None, bits_out=None, relu_bits=None, wino=None, wbits_out=None,
-                    relu_wbits=None, pool_code=None, addend=None, upsample2x=False, wp_version=1, dst_s2d=None):
-    """ONE call of ynet_conv2d_auto (include/ynet_hip.h): the library chooses the kernel family, splits wide layers and keeps the transformed
-    filters in a cache that lives in the layer's filter cache `wino[0]` under "auto_<direction>".  Operands as conv2d_raw; addend: (ptr,
-    image_stride, modulus); upsample2x: the source is the low-resolution map (H, W are the up-sampled size).  Returns (tag, YnetConvTaken)."""
-    lib = _lib()
+def _auto_desc(srcs, dsts, wp, B, H, W, K, flags, relu_of=None):
+    """A YnetConvAuto with the operands every form has: srcs / dsts lists of (ptr, channels, batch_stride[, batch modulus]), wp the filter's address, relu_of
+    (ptr, batch_stride)."""
     d = L.ConvAuto()
     d.nsrc, d.ndst = len(srcs), len(dsts)
     for i, s_ in enumerate(srcs):
@@ -584,14 +589,54 @@ def conv2d_auto_raw(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=None, 
         d.src_bmod[i] = s_[3] if len(s_) > 3 else 0
     for i, t_ in enumerate(dsts):
         d.dst[i], d.dst_c[i], d.dst_bs[i] = t_[0], t_[1], t_[2]
-        if dst_s2d is not None and dst_s2d[i]:
-            d.dst_s2d[i] = 1
-    if mask:
-        d.mask, d.mask_bs = mask[0], mask[1]
-    d.wp, d.bias = wp.data_ptr(), (bias.data_ptr() if bias is not None else None)
-    d.B, d.H, d.W, d.K, d.relu, d.upsample2x = B, H, W, K, 1 if relu else 0, 1 if upsample2x else 0
     if relu_of is not None:
         d.relu_of, d.relu_of_bs = relu_of[0], relu_of[1]
+    d.wp, d.B, d.H, d.W, d.K, d.flags = wp, B, H, W, K, flags
+    return d
+
+
+def _auto_call(d, cache, key, wp, device, wp_version=1, src=None, ring=0):
+    """ONE ynet_conv2d_auto call for the filled descriptor d; returns the YnetConvTaken.  cache: the layer's filter cache (None: the call keeps no transformed
+    filter).  The plan's filters live in the _AutoFilter cache[key + (layout,)], layout = ynet_conv2d_auto_cache_layout(d) (0: the plan keeps none) -- _filter's
+    rule: a batch or raster size whose plan lays its filters out differently gets an entry of its own, one with the same layout shares this one.  wp, wp_version:
+    the packed filter the entry is made from, and the version handed to the library; the up-convolution form (wp None) names its raw filter by src, the
+    weight's (data_ptr, _version), and the entry counts the versions.  ring: the launches of the call that are no Winograd launches (wino_stats)."""
+    lib = _lib()
+    ent = None
+    if cache is not None:
+        floats = ctypes.c_longlong(0)
+        layout = lib.ynet_conv2d_auto_cache_layout(ctypes.byref(d), ctypes.byref(floats))
+        if floats.value < 0:
+            L.check(1, lib)
+        if layout:
+            ent = _filter(cache, key + (layout,), wp, lambda: torch.empty(floats.value, device=device, dtype=torch.float32), _AutoFilter)
+            d.cache, d.cache_floats, d.cache_tag = ent.u.data_ptr(), ent.u.numel(), ent.tag
+            d.wp_version = int(wp_version) if src is None else ent.version_of(src)
+    if d.B * d.H * d.W <= 65536:                                 # small maps only (see ynet_conv2d_workspace_floats)
+        nws = lib.ynet_conv2d_auto_workspace_floats(ctypes.byref(d))
+        if nws > 0:
+            d.workspace, d.workspace_floats = _workspace(device, nws).data_ptr(), nws
+    tk = L.ConvTaken()
+    L.check(lib.ynet_conv2d_auto(ctypes.byref(d), ctypes.byref(tk), _stream()), lib)
+    if tk.transformed and ent is not None:
+        ent.made()
+    if tk.family:
+        _count_launches(tk.nlaunch - ring, slice_form=tk.family in (3, 5))
+    return tk
+
+
+def conv2d_auto_raw(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=None, pooled=None, bits_out=None, relu_bits=None, wino=None, wbits_out=None,
+                    relu_wbits=None, pool_code=None, addend=None, upsample2x=False, wp_version=1, dst_s2d=None):
+    """ONE call of ynet_conv2d_auto (include/ynet_hip.h): the library chooses the kernel family, splits wide layers and keeps the transformed
+    filters in a cache that lives in the layer's filter cache `wino[0]` under ("auto", <direction>, <layout>), one per layout (_auto_call).  Operands as
+    conv2d_raw; addend: (ptr, image_stride, modulus); upsample2x: the source is the low-resolution map (H, W are the up-sampled size).  Returns
+    (tag, YnetConvTaken)."""
+    d = _auto_desc(srcs, dsts, wp.data_ptr(), B, H, W, K, _auto_flags(wino), relu_of=relu_of)
+    for i, s2d in enumerate(dst_s2d or ()):
+        d.dst_s2d[i] = 1 if s2d else 0
+    if mask:
+        d.mask, d.mask_bs = mask[0], mask[1]
+    d.bias, d.relu, d.upsample2x = (bias.data_ptr() if bias is not None else None), 1 if relu else 0, 1 if upsample2x else 0
     if pooled is not None:
         d.pooled, d.pooled_bs = pooled[0], pooled[1]
         if pool_code is not None:
@@ -603,42 +648,8 @@ def conv2d_auto_raw(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=None, 
         d.wbits_out = wbits_out.data_ptr()
     if relu_wbits is not None:
         d.relu_wbits = relu_wbits.data_ptr()
-    d.flags = flags = _auto_flags(wino)
-    ent = None
-    if wino is not None and not (flags & L.AUTO_NO_WINOGRAD):
-        cache, what = wino
-        need = lib.ynet_conv2d_auto_cache_floats(ctypes.byref(d))
-        if need < 0:
-            L.check(1, lib)
-        if need > 0:
-            key = "auto_" + what
-            ent = cache.get(key)
-            if ent is None or ent[0] is not wp or ent[1].numel() < need:
-                ent = cache[key] = [wp, torch.empty(need, device=wp.device, dtype=torch.float32), (ctypes.c_ulonglong * 2)(0, 0), None, None]
-            elif ent[4] is not None and not torch.cuda.is_current_stream_capturing():
-                # (made on another stream a few microseconds ago -- evaluate()'s two sweep streams: wait for the maker's event, as _Filter.ready)
-                cur = torch.cuda.current_stream()
-                if cur.cuda_stream != ent[3] and not ent[4].query():
-                    cur.wait_event(ent[4])
-            d.cache, d.cache_floats, d.cache_tag, d.wp_version = ent[1].data_ptr(), ent[1].numel(), ent[2], int(wp_version)
-    if B * H * W <= 65536:                                       # small maps only (see ynet_conv2d_workspace_floats)
-        nws = lib.ynet_conv2d_auto_workspace_floats(ctypes.byref(d))
-        if nws > 0:
-            key = (wp.device, torch.cuda.current_stream().cuda_stream)   # grow-only scratch per stream (stream-ordered reuse)
-            ws = _conv_ws.get(key)
-            if ws is None or ws.numel() < nws:
-                ws = _conv_ws[key] = torch.empty(nws, device=wp.device, dtype=torch.float32)
-            d.workspace, d.workspace_floats = ws.data_ptr(), nws
-    tk = L.ConvTaken()
-    L.check(lib.ynet_conv2d_auto(ctypes.byref(d), ctypes.byref(tk), _stream()), lib)
-    if tk.transformed and ent is not None and torch.cuda.is_available() and not torch.cuda.is_current_stream_capturing():
-        ev = torch.cuda.Event()
-        ev.record()
-        ent[3], ent[4] = torch.cuda.current_stream().cuda_stream, ev
-    if tk.family:
-        wino_stats["launches"] += tk.nlaunch
-        if tk.family in (3, 5):
-            wino_stats["launches16"] = wino_stats.get("launches16", 0) + tk.nlaunch
+    cache, what = (None, None) if d.flags & L.AUTO_NO_WINOGRAD else wino      # (wino None or YNET_WINOGRAD=0: implicit GEMM only, no transformed filter)
+    tk = _auto_call(d, cache, ("auto", what), wp, wp.device, wp_version=wp_version)
     return _auto_tag(tk), tk
 
 
@@ -653,15 +664,10 @@ def dgrad_relu_family(B, H, W, dy_c, dx_c, K=3):
     key = (B, H, W, dy_c, dx_c, K, _wino_allowed, _wino16_allowed, _wino16_for_16)
     fam = _dgrad_family_memo.get(key)
     if fam is None:
-        d, tk = L.ConvAuto(), L.ConvTaken()
-        d.nsrc = d.ndst = 1
-        d.src[0], d.src_c[0], d.src_bs[0] = 256, dy_c, dy_c * H * W          # (alignment stand-ins: the callers check the real tensors)
-        d.dst[0], d.dst_c[0], d.dst_bs[0] = 256, dx_c, dx_c * H * W
-        d.relu_of, d.relu_of_bs = 256, dx_c * H * W
-        d.wp = 256
-        d.B, d.H, d.W, d.K = B, H, W, K
-        d.flags = (0 if _wino_allowed else L.AUTO_NO_WINOGRAD) | (0 if _wino16_allowed else L.AUTO_NO_WINOGRAD16) | (L.AUTO_WINOGRAD16_FOR_16 if _wino16_for_16 else 0)
-        lib = _lib()
+        flags = (0 if _wino_allowed else L.AUTO_NO_WINOGRAD) | (0 if _wino16_allowed else L.AUTO_NO_WINOGRAD16) | (L.AUTO_WINOGRAD16_FOR_16 if _wino16_for_16 else 0)
+        # (256: alignment stand-ins for the addresses -- the callers check the real tensors)
+        d = _auto_desc([(256, dy_c, dy_c * H * W)], [(256, dx_c, dx_c * H * W)], 256, B, H, W, K, flags, relu_of=(256, dx_c * H * W))
+        lib, tk = _lib(), L.ConvTaken()
         L.check(lib.ynet_conv2d_auto_plan(ctypes.byref(d), ctypes.byref(tk)), lib)
         fam = _dgrad_family_memo[key] = int(tk.family)
     return fam
@@ -865,10 +871,7 @@ def _conv2d_raw_py(srcs, mask, wp, bias, dsts, B, H, W, K, relu, relu_of=None, p
     if B * H * W <= 65536:                                       # small maps only (see ynet_conv2d_workspace_floats)
         nws = lib.ynet_conv2d_workspace_floats(B, H, W, sum(d[1] for d in dsts))
         if nws:
-            key = (wp.device, torch.cuda.current_stream().cuda_stream)   # grow-only scratch per stream (stream-ordered reuse)
-            ws = _conv_ws.get(key)
-            if ws is None or ws.numel() < nws:
-                ws = _conv_ws[key] = torch.empty(nws, device=wp.device, dtype=torch.float32)
+            ws = _workspace(wp.device, nws)
     if relu_of is not None:
         if len(srcs) != 1 or len(dsts) != 1 or bias is not None or relu:
             raise ValueError("conv2d_raw: relu_of is for a data gradient with one source and one destination")
@@ -979,6 +982,7 @@ class _Filter:
     """One transformed filter of a layer's cache: the tensor `u`, the filter `wp` it was made from (kept alive), and the stream and event of the launch
     that made it."""
     __slots__ = ("wp", "u", "stream", "event")
+    lazy = False      # make() of _filter enqueues the transform, which is then made()
 
     def __init__(self, wp, u):
         self.wp, self.u, self.stream, self.event = wp, u, None, None
@@ -1000,20 +1004,39 @@ class _Filter:
                 cur.wait_event(self.event)
 
 
-def _filter(cache: dict, key: tuple, wp, make):
+class _AutoFilter(_Filter):
+    """The filter cache of one layout of a ynet_conv2d_auto call (_auto_call): `u` is the buffer the library transforms into, inside the call, whenever `tag`
+    -- the two host words it keeps -- or the version it is given does not match; made() is due behind a call that reports taken->transformed.  The
+    up-convolution form's buffer is made from the layer's raw filter: `src` names it and `version` counts how often it moved (version_of)."""
+    __slots__ = ("tag", "src", "version")
+    lazy = True
+
+    def __init__(self, wp, u):
+        super().__init__(wp, u)
+        self.tag, self.src, self.version = (ctypes.c_ulonglong * 2)(0, 0), None, 0
+
+    def version_of(self, src):
+        if src != self.src:      # (a new filter: a new version, the library remakes the tables)
+            self.src, self.version = src, self.version + 1
+        return self.version
+
+
+def _filter(cache: dict, key: tuple, wp, make, entry=_Filter):
     """Find or make the transformed filter cache[key] of a layer's cache (the dict _cached clears when the layer's weights change): make() -> tensor enqueues
-    the transform of `wp` on the current stream; make None: None on a miss.  THE RULE: `key` names everything the layout depends on, so an entry is never
-    overwritten by another layout, resized or popped -- a captured graph reads it at its address for as long as the weights stand.  An entry is stale only
-    when it was made from another filter than `wp`, and is then made again under the same key: a caller that went around _cached, or the "rest" entries, whose
-    packed filter rest_filter re-packs (without clearing the dict) when the weight's version changes."""
+    the transform of `wp` on the current stream (a lazy entry's only allocates); make None: None on a miss.  THE RULE, true of every transformed filter the
+    package keeps -- ynet_conv2d_auto's caches included, whose key ends in ynet_conv2d_auto_cache_layout's value --: `key` names everything the layout depends
+    on, so an entry is never overwritten by another layout, resized or popped -- a captured graph reads it at its address for as long as the weights stand.
+    An entry is stale only when it was made from another filter than `wp`, and is then made again under the same key: a caller that went around _cached, or
+    the "rest" entries, whose packed filter rest_filter re-packs (without clearing the dict) when the weight's version changes."""
     ent = cache.get(key)
     if ent is not None and ent.wp is wp:
         ent.ready()
         return ent
     if make is None:
         return None
-    ent = cache[key] = _Filter(wp, make())
-    ent.made()
+    ent = cache[key] = entry(wp, make())
+    if not entry.lazy:
+        ent.made()
     return ent
 
 
@@ -1838,48 +1861,14 @@ def upconv_dgrad_raw(D, weight, dx, relu_of, B, cout, cin, h, w, cache):
     """dx [B, cin, h, w] = the data gradient of conv3x3(upsample2x(x), weight) from its output gradient written space-to-depth, D [B, 4 cout, h, w] (pointers; relu_of:
     the pointer of x when dx goes through x's ReLU backward, or None) -- ONE ynet_conv2d_auto call in the YNET_AUTO_UPCONV_BWD form: the library makes the effective
     filter and the ring tables from the raw filter (ynet_upconv_tables; upconv_s2d_tables is their Python twin) into a buffer of this layer's cache that belongs to
-    this form and this plan alone, then runs the low-resolution data gradient and the ring.  Returns the YnetConvTaken."""
-    lib = _lib()
-    wino = (cache, "dgrad")
-    if not torch.is_grad_enabled() and (h * w < _wino_eval_min_hw or not (_wino_plain_eval if 4 * cout in (16, 32) else _wino_cat_eval)):
-        wino = None      # (the gates conv2d_raw applies to the same data gradient)
+    this form and this layout alone -- ("upconv_bwd", <layout>): the batch sizes that share a plan share it --, then runs the low-resolution data gradient and the
+    ring.  Returns the YnetConvTaken."""
     hw = h * w
-    d = L.ConvAuto()
-    d.nsrc = d.ndst = 1
-    d.src[0], d.src_c[0], d.src_bs[0] = D, 4 * cout, 4 * cout * hw
-    d.dst[0], d.dst_c[0], d.dst_bs[0] = dx, cin, cin * hw
-    if relu_of is not None:
-        d.relu_of, d.relu_of_bs = relu_of, cin * hw
-    d.wp = weight.data_ptr()
-    d.B, d.H, d.W, d.K = B, h, w, 3
-    d.flags = _auto_flags(wino) | L.AUTO_UPCONV_BWD
-    need = lib.ynet_conv2d_auto_cache_floats(ctypes.byref(d))
-    if need <= 0:
-        L.check(1, lib)
-    # one buffer per plan: a captured step keeps reading the buffer of the plan it captured, whatever other batch sizes do eagerly in between
-    key = ("upconv_bwd", B, h, w, relu_of is not None, int(d.flags), int(need))
-    ent = cache.get(key)
-    if ent is None:
-        ent = cache[key] = [torch.empty(need, device=weight.device, dtype=torch.float32), (ctypes.c_ulonglong * 2)(0, 0), None, 0]
-    wkey = (weight.data_ptr(), weight._version)
-    if ent[2] != wkey:      # (a new filter: a new version, the library remakes the tables)
-        ent[2], ent[3] = wkey, ent[3] + 1
-    d.cache, d.cache_floats, d.cache_tag, d.wp_version = ent[0].data_ptr(), ent[0].numel(), ent[1], ent[3]
-    if B * hw <= 65536:                                          # small maps only (see ynet_conv2d_workspace_floats)
-        nws = lib.ynet_conv2d_auto_workspace_floats(ctypes.byref(d))
-        if nws > 0:
-            wkey_ = (weight.device, torch.cuda.current_stream().cuda_stream)
-            ws = _conv_ws.get(wkey_)
-            if ws is None or ws.numel() < nws:
-                ws = _conv_ws[wkey_] = torch.empty(nws, device=weight.device, dtype=torch.float32)
-            d.workspace, d.workspace_floats = ws.data_ptr(), nws
-    tk = L.ConvTaken()
-    L.check(lib.ynet_conv2d_auto(ctypes.byref(d), ctypes.byref(tk), _stream()), lib)
-    if tk.family:
-        wino_stats["launches"] += tk.nlaunch - 1      # (the ring is no Winograd launch)
-        if tk.family in (3, 5):
-            wino_stats["launches16"] = wino_stats.get("launches16", 0) + tk.nlaunch - 1
-    return tk
+    srcs = [(D, 4 * cout, 4 * cout * hw)]
+    wino = None if _wino_eval_gated(srcs, h, w) else (cache, "dgrad")      # (the gates conv2d_raw applies to the same data gradient)
+    d = _auto_desc(srcs, [(dx, cin, cin * hw)], weight.data_ptr(), B, h, w, 3, _auto_flags(wino) | L.AUTO_UPCONV_BWD,
+                   relu_of=None if relu_of is None else (relu_of, cin * hw))
+    return _auto_call(d, cache, ("upconv_bwd",), None, weight.device, src=(weight.data_ptr(), weight._version), ring=1)      # (the ring is no Winograd launch)
 
 
 def upconv_tables(weight, cache):

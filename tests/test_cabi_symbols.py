@@ -143,3 +143,29 @@ def test_conv2d_auto_plans_the_benchmarked_layers_without_a_gpu():
     assert lib.ynet_conv2d_auto_cache_layout(ctypes.byref(d), None) not in (0, up)
     d.flags, d.K = L.AUTO_UPCONV_BWD, 5      # no such form: 0, *floats = -1 and the reason
     assert lib.ynet_conv2d_auto_cache_layout(ctypes.byref(d), ctypes.byref(floats)) == 0 and floats.value == -1 and b"upconv_bwd" in lib.ynet_last_error()
+
+
+def test_one_layer_lays_its_filters_out_differently_at_two_batch_sizes():
+    """The premise of tests/test_gpu_auto_cache.py, on the host: each layer of tests/_auto_cache_cases.py takes another (family, variant, launches) at B 4 than
+    at B 8 on 128^2 maps, in the SAME number of cache floats and under different ynet_conv2d_auto_cache_layout values -- one buffer per (layer, direction) would
+    be overwritten in place; and the up-convolution's backward at 64^2 shares one layout between B 12 and B 32 and has another at B 8."""
+    import ctypes
+    import _auto_cache_cases as A
+    L = pkg("_lib")
+    lib = L.load()
+    for name, (cs, couts, dgrad, plans, floats) in A.LAYERS.items():
+        seen = {}
+        for B in A.BATCHES:
+            d, tk = A.descriptor(L, B, cs, couts, dgrad), L.ConvTaken()
+            assert lib.ynet_conv2d_auto_plan(ctypes.byref(d), ctypes.byref(tk)) == 0, lib.ynet_last_error()
+            assert (tk.family, tk.variant, tk.nlaunch) == plans[B], (name, B)
+            seen[B] = A.layout(L, lib, d)
+            assert seen[B][1] == floats == lib.ynet_conv2d_auto_cache_floats(ctypes.byref(d)), (name, B, seen[B])
+        assert 0 not in (seen[4][0], seen[8][0]) and seen[4][0] != seen[8][0], (name, seen)
+        assert A.layout(L, lib, A.descriptor(L, 2, cs, couts, dgrad)) == (0, 0), name      # (B 2: implicit GEMM, no transformed filter)
+        for B in (12, 32):
+            assert A.layout(L, lib, A.descriptor(L, B, cs, couts, dgrad)) == seen[8], (name, B)
+    for masked in (False, True):
+        l12, l32, l8 = (A.layout(L, lib, A.up_descriptor(L, B, masked)) for B in (12, 32, 8))
+        assert l12 == l32 and l8[0] not in (0, l12[0]) and l12[0] != 0, (masked, l12, l32, l8)
+    assert A.layout(L, lib, A.up_descriptor(L, 8, False)) != A.layout(L, lib, A.up_descriptor(L, 8, True))      # (the family-0 layouts of the two differ)
