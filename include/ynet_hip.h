@@ -78,7 +78,7 @@ int ynet_conv2d_last_launch(int which);
  * stage and the nn.MaxPool2d(2, 2) that opens the next one (models/ynet.py:202,215) without the stand-alone pass over y.
  * pooled [B][cout][H/2][W/2] (batch stride pooled_bs), the first-maximum / NaN rule of ynet_maxpool2_fwd; H, W even.
  * ynet_conv2d_pool_supported: 1 for the shapes that take it (3x3, W % 4 == 0, maps large enough for two-row tiles); the call fails
- * elsewhere, callers then run ynet_conv2d + ynet_maxpool2_fwd. */
+ * elsewhere before anything is launched (dst and pooled stay as they were), callers then run ynet_conv2d + ynet_maxpool2_fwd. */
 int ynet_conv2d_pool_supported(int B, int H, int W, int cout, int K);
 int ynet_conv2d_pool(const float* const* src, const int* src_c, const long long* src_bs, int nsrc, const float* wp, const float* bias,
                      float* dst, int cout, long long dst_bs, float* pooled, long long pooled_bs,

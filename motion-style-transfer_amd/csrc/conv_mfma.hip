@@ -2015,6 +2015,9 @@ int ynet_conv2d_pool(const float* const* src, const int* src_c, const long long*
                      float* dst, int cout, long long dst_bs, float* pooled, long long pooled_bs,
                      int B, int H, int W, int K, int relu, void* stream) {
     YNET_REQUIRE(dst != nullptr && pooled != nullptr, "conv2d_pool: null destination");
+    // (refused HERE, before anything is launched: outside these shapes conv_dispatch would run the plain kernel, which writes dst, and only
+    //  then find the pooled copy missing -- its check stays as a backstop)
+    YNET_REQUIRE(ynet_conv2d_pool_supported(B, H, W, cout, K), "conv2d_pool: shape B=%d %dx%d cout=%d is not served by the pooling epilogue (ask ynet_conv2d_pool_supported)", B, H, W, cout);
     float* dsts[1] = {dst};
     const int dc[1] = {cout};
     const long long db[1] = {dst_bs};
