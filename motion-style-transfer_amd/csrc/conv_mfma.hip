@@ -13,8 +13,8 @@
 //       by `buffer_load ... lds` (LDS-DMA) into a double buffer, scalar-only control code, buffer stores.
 //       The default for every 3x3 launch with >= 2 rows per wave or a folded (W <= 16) map.
 //   conv_mfma_kernel<K,NCB,R,CC,MASK,M16>   register-staged generation (global -> VGPR -> LDS): one-row launches
-//       of the 32^2..64^2 maps, 5x5, unaligned planes; M16 = false keeps the 32x32x2 tile form
-//       (M = 32 pixels, N = 32 channels, K = 2 channels).
+//       of the 32^2..64^2 maps, unaligned planes; 1x1 and 5x5 (M16 = false: the 32x32x2 tile form,
+//       M = 32 pixels, N = 32 channels, K = 2 channels).
 //   conv1x1_stream_kernel<CT,PX>            the HBM-bound 1x1 predictors (few channels) on the vector ALU.
 //   conv_split_reduce_kernel                sums the partials of a channel-split small-map launch (+bias, ReLU).
 //   pack_weight_kernel                      checkpoint layout -> packed [cin][tap][cout] (mode 1: flipped/transposed).
@@ -27,10 +27,6 @@
 #include "ynet_common.h"
 #include <stdlib.h>
 #include <stdio.h>
-
-#ifndef YNET_CC_NARROW
-#define YNET_CC_NARROW 8      // input channels staged per chunk by the Cout <= 32 kernels
-#endif
 
 struct ConvArgs {
     YSrc src[YNET_MAX_SRC];
@@ -50,10 +46,10 @@ struct ConvArgs {
     int addend_bmod;        //   repeat along the batch (evaluate()'s K goal samples share the encoder features), computed once
     const float* emask;     // optional [B][cout][H][W] post-ReLU activation whose backward is applied to the OUTPUT (one destination):
     long long emask_bs;     //   dst = emask > 0 ? conv(...) : 0 -- a data gradient written for a consumer that then needs no mask
-    int emask_done, pool_done;      //   (host side) the launched kernels applied it / wrote the pooled copy
+    int emask_done, pool_done;      //   (host side) emask_done: the launched kernels applied it; pool_done: unused (the plan says so before the launch)
     unsigned* bits_out;     // optional: the epilogue of a ReLU convolution also writes the 1-bit form of its activation mask (y > 0), in the
     const unsigned* bits_in;        //   register layout of its own tiles [tile][256 lanes][WPL words]; bits_in: a data gradient applies such a mask
-    int bits_done;                  //   (written by the forward convolution with the SAME output shape, hence the same tiling) instead of emask
+    int bits_done;                  //   (written by the forward convolution with the SAME output shape, hence the same tiling) instead of emask; bits_done: unused
     float* pool;            // optional second output [B][cout][H/2][W/2] = MaxPool2d(2, 2) of the (post-ReLU) first one, written by
     long long pool_bs;      //   the epilogue (conv_dma_pool_kernel): models/ynet.py:202,215 without the stand-alone pass over y
     int vec_store;          // 16-byte epilogue stores are legal (W % 4 == 0, aligned destinations)
@@ -1214,13 +1210,49 @@ __global__ __launch_bounds__(256, 2) void conv_dma_emaskb_kernel(const ConvArgs)
     conv_dma_body<NCB, R, CC, MASK, X4, FOLD, 5>();
 }
 
+// ================================================================================================
+// Host side.  make_direct_plan decides which kernel a call takes (pure host arithmetic: no HIP call, no allocation);
+// conv_dispatch_kernels maps the plan's fields to a template instantiation and launches it; the shape queries of the C ABI
+// (ynet_conv2d_plan, ynet_conv2d_*_supported, ynet_conv2d_relu_bits_words) read the same plan.
+// ================================================================================================
+
+// The development switches of this dispatcher (A/B measurements only), read from the environment once per process.
+struct ConvGates {
+    int dma;            // YNET_CONV_DMA: the LDS-DMA generation (0: every call takes the register-staged tiles)
+    int fold;           // YNET_CONV_FOLD: folded row units for maps no wider than 16 / 8 pixels
+    // YNET_CONV_NARROW: work items a launch is narrowed towards (0: off).  Measured on the captured C2 step (MI355X): target 0 / 512 /
+    // 1024 / 2048 / 4096 work items -> 9.78 / 9.69 / 9.63 / 9.56 / 9.55 ms at B = 32 and 4.05 / 3.88 / 3.84 / 3.79 / 3.79 ms at the
+    // reference scripts' batch of 10; the 16^2 .. 64^2 layers need less (or no) split of the channel loop with it.
+    int narrow;
+    int rows;           // YNET_CONV_R: 1 / 2 / 4 forces the rows per wave
+    int r4_min;         // YNET_CONV_R4_MIN: four rows per wave from this many four-row units
+    // YNET_CONV_R2_MIN: two rows per wave from this many two-row units (round 4: 512 -> 64.  At the reference scripts' batch of 10 the
+    // 32^2 / 64^2 layers fell below 512 two-row units and took the register-staged one-row kernel at 17-25 TFLOP/s; the two-row LDS-DMA
+    // tile runs them at 22-37: captured step 3.49 -> 3.44 ms at B 10, 8.93 -> 8.90 at B 32; 32 and 128 measure the same as 64)
+    int r2_min;
+    int stream1;        // YNET_CONV_1X1_STREAM: the streaming kernel for the 1x1 predictors
+    int no_ksplit;      // YNET_CONV_NO_KSPLIT (set, to any value): never split the channel loop
+    int ksplit_items;   // YNET_KSPLIT_ITEMS: launches with fewer work items than this are split ...
+    int ksplit_target;  // YNET_KSPLIT_TARGET: ... towards this many
+    int relu_bits;      // YNET_RELU_BITS: the 1-bit activation masks (0: ynet_conv2d_relu_bits_words serves no shape)
+    int debug;          // YNET_CONV_DEBUG -> ConvArgs::debug
+};
+
+static const ConvGates& conv_gates() {
+    static const ConvGates g = {ynet_env_int("YNET_CONV_DMA", 1),        ynet_env_int("YNET_CONV_FOLD", 1),
+                                ynet_env_int("YNET_CONV_NARROW", 2048),  ynet_env_int("YNET_CONV_R", 0),
+                                ynet_env_int("YNET_CONV_R4_MIN", 1024),  ynet_env_int("YNET_CONV_R2_MIN", 64),
+                                ynet_env_int("YNET_CONV_1X1_STREAM", 1), getenv("YNET_CONV_NO_KSPLIT") ? 1 : 0,
+                                ynet_env_int("YNET_KSPLIT_ITEMS", 256),  ynet_env_int("YNET_KSPLIT_TARGET", 512),
+                                ynet_env_int("YNET_RELU_BITS", 1),       ynet_env_int("YNET_CONV_DEBUG", 0)};
+    return g;
+}
+
 // Split of the input-channel loop over workgroups for launches with fewer work items than CUs.
 static int conv_ksplit(long long items, int nchunks) {
-    static const int off = getenv("YNET_CONV_NO_KSPLIT") ? 1 : 0;
-    static const int min_items = getenv("YNET_KSPLIT_ITEMS") ? atoi(getenv("YNET_KSPLIT_ITEMS")) : 256;
-    static const int target = getenv("YNET_KSPLIT_TARGET") ? atoi(getenv("YNET_KSPLIT_TARGET")) : 512;
-    if (off || items >= min_items || nchunks < 4) return 1;
-    long long k = (target + items - 1) / items;
+    const ConvGates& g = conv_gates();
+    if (g.no_ksplit || items >= g.ksplit_items || nchunks < 4) return 1;
+    long long k = (g.ksplit_target + items - 1) / items;
     if (k > nchunks / 2) k = nchunks / 2;
     if (k > 8) k = 8;
     return k < 1 ? 1 : (int)k;
@@ -1266,18 +1298,147 @@ __global__ __launch_bounds__(256) void conv_split_reduce_kernel(const SplitReduc
     }
 }
 
-template <int KS, int NCB, int R, int CC, bool MASK, bool M16>
-static int launch_conv_m(ConvArgs& a, hipStream_t st) {
-    using C = ConvCfg<KS, NCB, R, CC, M16>;
-    a.tiles_x = ceil_div(a.W, C::TW);
-    a.tiles_y = ceil_div(a.H, C::TH);
-    a.cgroups = ceil_div(a.cout, C::CB);
+// ------------------------------------------------------------------------------------------------
+// The launch plan: everything the choice of a kernel consists of, from everything it depends on.
+// ------------------------------------------------------------------------------------------------
+enum { GEN_NONE = 0, GEN_REG = 1, GEN_DMA = 2, GEN_FOLD = 3, GEN_STREAM = 4 };      // 1 .. 4: the kind ynet_note_launch reports in bits 0 .. 3
+enum { EPI_PLAIN = 0, EPI_ADD = 1, EPI_EMASK = 2, EPI_POOL = 3, EPI_BITS_OUT = 4, EPI_BITS_IN = 5 };      // conv_dma_body's EPI
+
+struct DirectCall {
+    int B, H, W, cout, K;       // cout: the channels left after the unwanted trailing destinations are dropped
+    bool vec_load, vec_store;   // 16-byte loads / stores are legal (ConvArgs::vec_load / vec_store)
+    bool mask, emask, pool, bits_out, bits_in, addend;      // the operand is present
+    bool addend_ok;             // one destination, the additive term 16-byte aligned
+    bool stream_ok;             // one source that does not repeat along the batch, one wanted destination (the 1x1 streaming kernel)
+};
+
+struct DirectPlan {
+    int gen;            // GEN_*: register-staged / LDS-DMA / folded LDS-DMA / 1x1 stream; GEN_NONE: no kernel serves the call
+    int nt16;           // 16-channel tiles the output channels are cut into (0: 32-channel blocks -- 1x1, 5x5)
+    int tiles, cb;      // tiles (blocks) per workgroup = the kernels' NCB, and its output channels; stream: 16 tiles output channels per thread
+    int rows, fold, cc; // rows per wave, folded row units (1: none), input channels per staged chunk
+    bool may_split;     // the channel loop may be split over workgroups (where the caller gave a workspace)
+    int epi;            // EPI_*: the epilogue extra the kernel itself applies (unfolded LDS-DMA tiles only; an output mask is applied
+                        // elsewhere by the reduction of a split channel loop or a pass of its own, the other extras nowhere else)
+};
+
+// Rows per wave (R): 4 gives the most operand reuse; small feature maps (8^2 .. 64^2) take R = 2 or 1
+// so that the launch still spreads over the 256 CUs (a workgroup's run time is its MFMA count).
+static int pick_rows(const DirectCall& c, int cb) {
+    const ConvGates& g = conv_gates();
+    if (g.rows == 1 || g.rows == 2 || g.rows == 4) return g.rows;
+    const long long per_img_x = ceil_div(c.W, 32), cg = ceil_div(c.cout, cb);
+    for (int r = 4; r > 1; r >>= 1) {
+        const long long nblk = per_img_x * ceil_div(c.H, 4 * r) * cg * c.B;
+        if (nblk >= (r == 4 ? g.r4_min : g.r2_min)) return r;
+    }
+    return 1;
+}
+
+// Rows per wave of a launch with nt16 16-channel tiles per workgroup: pick_rows, but at most two with three or four tiles (four rows of
+// them need more accumulators than a lane has registers: the register-staged kernel would spill, the LDS-DMA kernel has no such form).
+static int dma_rows(const DirectCall& c, int nt16) {
+    const int rows = pick_rows(c, 16 * nt16);
+    return (nt16 >= 3 && rows == 4) ? 2 : rows;
+}
+
+// The 16-channel tiles of a 3x3 layer: Cout is padded to 16 / 32 / 48 / 64 per workgroup
+static int m16_tiles(int cout) { return cout <= 16 ? 1 : (cout <= 32 ? 2 : (cout <= 48 ? 3 : 4)); }
+
+static int conv_fold(int H, int W) {
+    if (!conv_gates().fold) return 1;
+    if (W <= 8 && (H & 3) == 0) return 4;
+    if (W <= 16 && (H & 1) == 0) return 2;
+    return 1;
+}
+
+// Small and mid-size maps: fewer output channels per workgroup -> more workgroups.  A 64 -> 64 layer on B x 32^2 pixels is 256
+// row units: with all 64 output channels in one workgroup that is ONE workgroup per CU (one wave per SIMD, nothing to hide
+// its staging latency behind); 16 channels per workgroup give four per CU and the same MFMA count in total (the input tile
+// is then staged by four workgroups instead of one -- from L2).
+static int narrow_tiles(const DirectCall& c, int nt16, int fold) {
+    const int target = conv_gates().narrow;
+    if (target <= 0 || nt16 <= 1) return nt16;
+    const long long units = (long long)c.B * ceil_div(c.W, 32 / fold) * ceil_div(c.H, 4 * fold);      // one-row-per-wave tiles
+    int n = nt16;
+    while (n > 1 && units * ceil_div(nt16, n) < target) n = n > 2 ? 2 : 1;
+    return n;
+}
+
+static DirectPlan make_direct_plan(const DirectCall& c) {
+    const ConvGates& g = conv_gates();
+    DirectPlan p{};
+    p.fold = 1;
+    p.epi = EPI_PLAIN;
+    const int full = c.K == 3 ? m16_tiles(c.cout) : 0, fold = conv_fold(c.H, c.W);
+    p.nt16 = c.addend ? full : narrow_tiles(c, full, fold);       // (the additive-term kernels exist for two and four tiles only)
+    // 3x3 on 16-byte aligned operands: the LDS-DMA generation -- folded row units for maps no wider than 16 / 8 pixels, else tiles of
+    // two or four rows per wave; a map too small for two-row units goes on to the register-staged one-row kernel.
+    if (p.nt16 && g.dma && c.vec_load && c.vec_store) {
+        const int rows = fold > 1 ? 1 : dma_rows(c, p.nt16);
+        if (fold > 1 || rows >= 2) {
+            p.gen = fold > 1 ? GEN_FOLD : GEN_DMA;
+            p.tiles = p.nt16;
+            p.cb = 16 * p.nt16;
+            p.rows = rows;
+            p.fold = fold;
+            // CC = 4 input channels (one K-step of the 16x16x4 MFMA) per chunk: 34-60 KB of LDS for both buffers, so 3-4 workgroups stay
+            // resident per CU (measured 5-10 % faster than CC = 8 with 2 resident workgroups).  The small tiles (folded maps, two rows of one
+            // tile) take CC 8: a chunk of 4 channels is 18 .. 72 MFMAs per wave there -- 0.3 .. 1 us -- behind a DMA round trip of ~1.3 us
+            // that the one-chunk-ahead pipeline cannot hide.  (Deeper chunks gain nothing: DESIGN.md section 4.17.)
+            p.cc = (p.tiles <= 2 && (fold > 1 || (rows == 2 && p.tiles == 1))) ? 8 : 4;
+            if (p.gen == GEN_DMA) {
+                if (c.addend) p.epi = EPI_ADD;
+                else if (c.bits_in) p.epi = EPI_BITS_IN;
+                else if (c.bits_out && !c.mask) p.epi = EPI_BITS_OUT;
+                else if (c.emask) p.epi = EPI_EMASK;
+                else if (c.pool && !c.mask) p.epi = EPI_POOL;
+            }
+            p.may_split = p.epi == EPI_PLAIN || p.epi == EPI_EMASK;
+        }
+    }
+    if (c.addend) {     // what evaluate()'s shared skip features need, nothing more; callers ask ynet_conv2d_add_supported first
+        if (!(p.epi == EPI_ADD && (p.tiles == 2 || p.tiles == 4) && !c.mask && c.addend_ok)) p.gen = GEN_NONE;
+        return p;
+    }
+    if (p.gen != GEN_NONE) return p;
+    if (c.K == 1 && g.stream1 && c.stream_ok && !c.mask && c.cout <= 32 && c.vec_store && c.vec_load && ((long long)c.H * c.W) % 4 == 0) {
+        p.gen = GEN_STREAM;
+        p.tiles = c.cout <= 16 ? 1 : 2;
+        p.cb = 16 * p.tiles;
+        return p;
+    }
+    p.gen = (c.K == 1 || c.K == 3 || c.K == 5) ? GEN_REG : GEN_NONE;
+    p.may_split = true;
+    if (p.nt16) {
+        p.tiles = p.nt16;
+        p.cb = 16 * p.nt16;
+        p.rows = dma_rows(c, p.nt16);
+        p.cc = 8;
+    } else {
+        p.tiles = c.cout > 32 ? 2 : 1;
+        p.cb = 32 * p.tiles;
+        p.rows = c.K == 5 ? 4 : pick_rows(c, p.cb);
+        p.cc = c.K == 1 ? 16 : 4;
+    }
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Launches: plan fields -> template arguments.  Nothing below decides anything.
+// ------------------------------------------------------------------------------------------------
+// The tile launch both generations share: tile counts, the split of the channel loop under the workspace cap, the persistent grid and
+// the reduction of a split.  `slots`: resident workgroups of this instantiation on this device (0: not asked yet).
+static int conv_launch_tiles(ConvArgs& a, const DirectPlan& p, const void* kernel, int lds_bytes, int& slots, hipStream_t st) {
+    a.tiles_x = ceil_div(a.W, 32 / p.fold);
+    a.tiles_y = ceil_div(a.H, 4 * p.rows * p.fold);
+    a.cgroups = ceil_div(a.cout, p.cb);
     long long nt = (long long)a.tiles_x * a.tiles_y * a.cgroups * a.B;
     {   // small maps: split the channel chunks over several workgroups (partials summed by a second kernel)
         int nchunks = 0;
-        for (int i = 0; i < a.nsrc; ++i) nchunks += ceil_div(a.src[i].c, CC);
+        for (int i = 0; i < a.nsrc; ++i) nchunks += ceil_div(a.src[i].c, p.cc);
         a.ksplit = 1;
-        if (a.partial != nullptr) a.ksplit = conv_ksplit(nt, nchunks);
+        if (a.partial != nullptr && p.may_split) a.ksplit = conv_ksplit(nt, nchunks);
         while (a.ksplit > 1 && (long long)a.ksplit * a.B * a.cout * a.H * a.W > a.partial_cap) --a.ksplit;
         a.cps = ceil_div(nchunks, a.ksplit);
         a.ksplit = ceil_div(nchunks, a.cps);          // no empty split
@@ -1285,15 +1446,11 @@ static int launch_conv_m(ConvArgs& a, hipStream_t st) {
     }
     YNET_REQUIRE(nt > 0 && nt < (1ll << 31), "conv2d: %lld tiles are out of range", nt);
     a.ntiles = (int)nt;
-    static const int debug = getenv("YNET_CONV_DEBUG") ? atoi(getenv("YNET_CONV_DEBUG")) : 0;
-    a.debug = debug;
-    static int slots_dev[YNET_MAX_DEV] = {0};          // resident workgroups on the device for this instantiation
-    int& slots = slots_dev[ynet_device_slot()];
+    a.debug = conv_gates().debug;
     if (slots == 0) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<KS, NCB, R, CC, MASK, M16>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
+        (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
         int per_cu = 0, dev = 0, cus = 256;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv_mfma_kernel<KS, NCB, R, CC, MASK, M16>, 256, C::LDS_BYTES);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds_bytes);
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         if (per_cu < 1) per_cu = 1;
@@ -1301,8 +1458,10 @@ static int launch_conv_m(ConvArgs& a, hipStream_t st) {
         slots = per_cu * cus;
     }
     const long long nblk = nt < slots ? nt : slots;
-    ynet_note_launch(0, 1 | (R << 4) | (a.ksplit << 8) | (a.vec_load << 12) | (a.vec_store << 13));
-    hipLaunchKernelGGL((conv_mfma_kernel<KS, NCB, R, CC, MASK, M16>), dim3((unsigned)nblk), dim3(256), C::LDS_BYTES, st, a);
+    ynet_note_launch(0, p.gen | (p.rows << 4) | (a.ksplit << 8) | (a.vec_load << 12) | (a.vec_store << 13));
+    void* kargs[] = {&a};
+    (void)hipLaunchKernel(kernel, dim3((unsigned)nblk), dim3(256), kargs, lds_bytes, st);
+    const bool reduce_emask = p.gen != GEN_REG;       // (the register-staged generation leaves the output mask to conv_emask_kernel)
     if (a.ksplit > 1) {
         SplitReduceArgs r{};
         r.partial = a.partial;
@@ -1314,215 +1473,90 @@ static int launch_conv_m(ConvArgs& a, hipStream_t st) {
         r.cout = a.cout;
         r.HW = a.H * a.W;
         r.relu = a.relu;
+        if (reduce_emask) {
+            r.emask = a.emask;
+            r.emask_bs = a.emask_bs;
+        }
         long long n4 = (long long)a.B * a.cout * (r.HW / 4);
         int grid = (int)((n4 + 255) / 256);
         if (grid > 2048) grid = 2048;
         hipLaunchKernelGGL(conv_split_reduce_kernel, dim3(grid), dim3(256), 0, st, r);
     }
+    a.emask_done = p.epi == EPI_EMASK || (reduce_emask && a.ksplit > 1);      // (in the epilogue, or in the reduction of a split channel loop)
     return ynet_check_launch("conv2d");
 }
 
-template <int KS, int NCB, int R, int CC, bool M16 = false>
-static int launch_conv(ConvArgs& a, hipStream_t st) {
-    return a.mask ? launch_conv_m<KS, NCB, R, CC, true, M16>(a, st) : launch_conv_m<KS, NCB, R, CC, false, M16>(a, st);
+template <int KS, int NCB, int R, int CC, bool M16>
+static int launch_conv(ConvArgs& a, const DirectPlan& p, hipStream_t st) {
+    static int slots_m[YNET_MAX_DEV] = {0}, slots_p[YNET_MAX_DEV] = {0};      // (per instantiation and per device)
+    const int dev = ynet_device_slot();
+    if (a.mask) return conv_launch_tiles(a, p, reinterpret_cast<const void*>(&conv_mfma_kernel<KS, NCB, R, CC, true, M16>), ConvCfg<KS, NCB, R, CC, M16>::LDS_BYTES, slots_m[dev], st);
+    return conv_launch_tiles(a, p, reinterpret_cast<const void*>(&conv_mfma_kernel<KS, NCB, R, CC, false, M16>), ConvCfg<KS, NCB, R, CC, M16>::LDS_BYTES, slots_p[dev], st);
 }
 
-// Rows per wave (R): 4 gives the most operand reuse; small feature maps (8^2 .. 64^2) take R = 2 or 1
-// so that the launch still spreads over the 256 CUs (a workgroup's run time is its MFMA count).
-static int pick_rows(const ConvArgs& a, int cb) {
-    static const int forced = getenv("YNET_CONV_R") ? atoi(getenv("YNET_CONV_R")) : 0;
-    if (forced == 1 || forced == 2 || forced == 4) return forced;
-    static const int r4_min = getenv("YNET_CONV_R4_MIN") ? atoi(getenv("YNET_CONV_R4_MIN")) : 1024;
-    // (round 4: 512 -> 64.  At the reference scripts' batch of 10 the 32^2 / 64^2 layers fell below 512 two-row units and took the
-    //  register-staged one-row kernel at 17-25 TFLOP/s; the two-row LDS-DMA tile runs them at 22-37: captured step 3.49 -> 3.44 ms at
-    //  B 10, 8.93 -> 8.90 at B 32; 32 and 128 measure the same as 64)
-    static const int r2_min = getenv("YNET_CONV_R2_MIN") ? atoi(getenv("YNET_CONV_R2_MIN")) : 64;
-    const long long per_img_x = ceil_div(a.W, 32), cg = ceil_div(a.cout, cb);
-    for (int r = 4; r > 1; r >>= 1) {
-        const long long nblk = per_img_x * ceil_div(a.H, 4 * r) * cg * a.B;
-        if (nblk >= (r == 4 ? r4_min : r2_min)) return r;
-    }
+static int launch_plan_reg(ConvArgs& a, const DirectPlan& p, int K, hipStream_t st) {
+#define REG_CASE(KS, NCB, R, CC, M16) \
+    if (K == KS && p.tiles == NCB && p.rows == R && p.cc == CC) return launch_conv<KS, NCB, R, CC, M16>(a, p, st)
+    REG_CASE(3, 1, 4, 8, true);  REG_CASE(3, 1, 2, 8, true);  REG_CASE(3, 1, 1, 8, true);
+    REG_CASE(3, 2, 4, 8, true);  REG_CASE(3, 2, 2, 8, true);  REG_CASE(3, 2, 1, 8, true);
+    REG_CASE(3, 3, 2, 8, true);  REG_CASE(3, 3, 1, 8, true);
+    REG_CASE(3, 4, 2, 8, true);  REG_CASE(3, 4, 1, 8, true);
+    REG_CASE(1, 1, 4, 16, false); REG_CASE(1, 1, 2, 16, false); REG_CASE(1, 1, 1, 16, false);
+    REG_CASE(1, 2, 4, 16, false); REG_CASE(1, 2, 2, 16, false); REG_CASE(1, 2, 1, 16, false);
+    REG_CASE(5, 1, 4, 4, false);  REG_CASE(5, 2, 4, 4, false);
+#undef REG_CASE
+    ynet_set_error("conv2d: no register-staged kernel for K=%d tiles=%d rows=%d", K, p.tiles, p.rows);
     return 1;
 }
 
-// Rows per wave of an LDS-DMA launch with nt16 16-channel tiles per workgroup.  Where pick_rows says 4, the two-tile kernel (Cout 17 .. 32 per
-// workgroup: the level-3 / level-4 layers of both decoders) takes THREE (round 4): 48 accumulator registers instead of 64 -> <= 96 VGPRs
-// -> five resident workgroups per CU instead of four, the occupancy at which the 48-channel kernel <3,2,4> reaches 0.92 MFMA-busy against
-// 0.85 for <2,4,4>; the map's height need not divide by 12 (the last row unit is cut by the range checks).  A launch with the pooled copy
-// keeps 4 (its epilogue pairs rows inside a wave's rows).
-static int dma_rows(const ConvArgs& a, int nt16) {
-    static const int r3 = getenv("YNET_CONV_R3") ? atoi(getenv("YNET_CONV_R3")) : 0;
-    int rows = pick_rows(a, 16 * nt16);
-    if (nt16 >= 3 && rows == 4) rows = 2;
-    if (r3 && nt16 == 2 && rows == 4 && a.pool == nullptr) rows = 3;
-    return rows;
-}
-
-template <int NCB, int R, int CC, bool MASK, bool X4, int FOLD, int EPI = 0>
-static int launch_dma_m(ConvArgs& a, hipStream_t st) {
-    using C = DmaCfg<NCB, R, CC, MASK, X4, FOLD>;
-    constexpr bool ADD = EPI == 1;
+// Only the quad-DMA form (X4) is instantiated: the plan asks for vec_load.
+template <int NCB, int R, int CC, bool MASK, int FOLD, int EPI>
+static int launch_dma_m(ConvArgs& a, const DirectPlan& p, hipStream_t st) {
     const auto KERNEL = [] {       // (if constexpr: only the wanted instantiation is compiled)
-        if constexpr (EPI == 1) return &conv_dma_add_kernel<NCB, R, CC, MASK, X4, FOLD>;
-        else if constexpr (EPI == 2) return &conv_dma_emask_kernel<NCB, R, CC, MASK, X4, FOLD>;
-        else if constexpr (EPI == 3) return &conv_dma_pool_kernel<NCB, R, CC, MASK, X4, FOLD>;
-        else if constexpr (EPI == 4) return &conv_dma_bits_kernel<NCB, R, CC, MASK, X4, FOLD>;
-        else if constexpr (EPI == 5) return &conv_dma_emaskb_kernel<NCB, R, CC, MASK, X4, FOLD>;
-        else return &conv_dma_kernel<NCB, R, CC, MASK, X4, FOLD>;
+        if constexpr (EPI == EPI_ADD) return &conv_dma_add_kernel<NCB, R, CC, MASK, true, FOLD>;
+        else if constexpr (EPI == EPI_EMASK) return &conv_dma_emask_kernel<NCB, R, CC, MASK, true, FOLD>;
+        else if constexpr (EPI == EPI_POOL) return &conv_dma_pool_kernel<NCB, R, CC, MASK, true, FOLD>;
+        else if constexpr (EPI == EPI_BITS_OUT) return &conv_dma_bits_kernel<NCB, R, CC, MASK, true, FOLD>;
+        else if constexpr (EPI == EPI_BITS_IN) return &conv_dma_emaskb_kernel<NCB, R, CC, MASK, true, FOLD>;
+        else return &conv_dma_kernel<NCB, R, CC, MASK, true, FOLD>;
     }();
-    a.tiles_x = ceil_div(a.W, C::TW);
-    a.tiles_y = ceil_div(a.H, C::TH);
-    a.cgroups = ceil_div(a.cout, C::CB);
-    long long nt = (long long)a.tiles_x * a.tiles_y * a.cgroups * a.B;
-    {
-        int nchunks = 0;
-        for (int i = 0; i < a.nsrc; ++i) nchunks += ceil_div(a.src[i].c, CC);
-        a.ksplit = 1;
-        if (a.partial != nullptr && !ADD && EPI < 3) a.ksplit = conv_ksplit(nt, nchunks);
-        while (a.ksplit > 1 && (long long)a.ksplit * a.B * a.cout * a.H * a.W > a.partial_cap) --a.ksplit;
-        a.cps = ceil_div(nchunks, a.ksplit);
-        a.ksplit = ceil_div(nchunks, a.cps);
-        nt *= a.ksplit;
-    }
-    YNET_REQUIRE(nt > 0 && nt < (1ll << 31), "conv2d: %lld tiles are out of range", nt);
-    a.ntiles = (int)nt;
-    static const int debug = getenv("YNET_CONV_DEBUG") ? atoi(getenv("YNET_CONV_DEBUG")) : 0;
-    a.debug = debug;
-    static int slots_dev[YNET_MAX_DEV] = {0};
-    int& slots = slots_dev[ynet_device_slot()];
-    if (slots == 0) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        int per_cu = 0, dev = 0, cus = 256;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KERNEL, 256, C::LDS_BYTES);
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (per_cu < 1) per_cu = 1;
-        if (cus < 1) cus = 256;
-        slots = per_cu * cus;
-    }
-    const long long nblk = nt < slots ? nt : slots;
-    ynet_note_launch(0, (FOLD > 1 ? 3 : 2) | (R << 4) | (a.ksplit << 8) | (a.vec_load << 12) | (a.vec_store << 13));
-    hipLaunchKernelGGL((KERNEL), dim3((unsigned)nblk), dim3(256), C::LDS_BYTES, st, a);
-    if (a.ksplit > 1) {
-        SplitReduceArgs r{};
-        r.partial = a.partial;
-        r.bias = a.bias;
-        for (int i = 0; i < a.ndst; ++i) r.dst[i] = a.dst[i];
-        r.ndst = a.ndst;
-        r.ksplit = a.ksplit;
-        r.B = a.B;
-        r.cout = a.cout;
-        r.HW = a.H * a.W;
-        r.relu = a.relu;
-        r.emask = a.emask;
-        r.emask_bs = a.emask_bs;
-        long long n4 = (long long)a.B * a.cout * (r.HW / 4);
-        int grid = (int)((n4 + 255) / 256);
-        if (grid > 2048) grid = 2048;
-        hipLaunchKernelGGL(conv_split_reduce_kernel, dim3(grid), dim3(256), 0, st, r);
-    }
-    if (EPI == 2 || a.ksplit > 1) a.emask_done = 1;       // (in the epilogue, or in the reduction of a split channel loop)
-    if (EPI == 3) a.pool_done = 1;
-    if (EPI == 4 || EPI == 5) a.bits_done = 1;
-    return ynet_check_launch("conv2d");
+    static int slots_dev[YNET_MAX_DEV] = {0};          // resident workgroups on the device for this instantiation
+    return conv_launch_tiles(a, p, reinterpret_cast<const void*>(KERNEL), DmaCfg<NCB, R, CC, MASK, true, FOLD>::LDS_BYTES, slots_dev[ynet_device_slot()], st);
 }
 
-// CC = 4 input channels (one K-step of the 16x16x4 MFMA) per chunk: 34-60 KB of LDS for both buffers, so
-// 3-4 workgroups stay resident per CU (measured 5-10 % faster than CC = 8 with 2 resident workgroups).
-// Only the quad-DMA form is instantiated (callers check a.vec_load).
-// Small tiles (one or two rows per wave of <= 32 output channels, folded maps) take DEEPER chunks: a chunk of 4 channels is
-// 18 .. 72 MFMAs per wave there -- 0.3 .. 1 us -- behind a DMA round trip of ~1.3 us that the one-chunk-ahead pipeline cannot
-// hide (a 64 -> 64 layer on a 16^2 map ran 16 chunks x 1.3 us = 21 us for 0.6 GFLOP); YNET_CONV_SMALL_CC chunks of 8 or 16
-// channels make it 8 or 4 round trips (their LDS tiles are small).
-static int small_cc() {
-    // Round 4 measured 8 / 16 / 32 with the flat DMA items (captured C2 step, one box): 8.92 / 8.95 / 9.00 ms at B 32 and 3.53 / 3.56 /
-    // 3.56 ms at B 10; per-kernel averages of the folded tiles in the serial trace 17.6 / - / 17.4 us (16^2) and 21.3 / - / 23.8 us (8^2):
-    // the number of DMA round trips is NOT what bounds these launches, so the default stays 8.
-    static const int cc = getenv("YNET_CONV_SMALL_CC") ? atoi(getenv("YNET_CONV_SMALL_CC")) : 8;
-    return cc;
-}
-
-template <int NCB, int R, int FOLD = 1, int CC = 4>
-static int launch_dma(ConvArgs& a, hipStream_t st) {
-    if constexpr (R >= 2 && FOLD == 1) {      // the large-map tiles (ynet_conv2d_dgrad_relu_supported)
-        if (a.bits_in) return a.mask ? launch_dma_m<NCB, R, CC, true, true, FOLD, 5>(a, st) : launch_dma_m<NCB, R, CC, false, true, FOLD, 5>(a, st);
-        if (a.bits_out && !a.mask) return launch_dma_m<NCB, R, CC, false, true, FOLD, 4>(a, st);
-        if (a.emask) return a.mask ? launch_dma_m<NCB, R, CC, true, true, FOLD, 2>(a, st) : launch_dma_m<NCB, R, CC, false, true, FOLD, 2>(a, st);
-        if constexpr (R % 2 == 0) {
-            if (a.pool && !a.mask) return launch_dma_m<NCB, R, CC, false, true, FOLD, 3>(a, st);
+// plan.epi and the input-side mask -> the kernel form.  The pooled copy and the written bit mask exist without an input-side mask only,
+// the additive term for two and four tiles without one, and the folded tiles are plain.
+template <int NCB, int R, int CC, int FOLD>
+static int launch_dma(ConvArgs& a, const DirectPlan& p, hipStream_t st) {
+    const bool m = a.mask != nullptr;
+    if constexpr (FOLD == 1) {
+        if (p.epi == EPI_BITS_IN) return m ? launch_dma_m<NCB, R, CC, true, 1, EPI_BITS_IN>(a, p, st) : launch_dma_m<NCB, R, CC, false, 1, EPI_BITS_IN>(a, p, st);
+        if (p.epi == EPI_EMASK) return m ? launch_dma_m<NCB, R, CC, true, 1, EPI_EMASK>(a, p, st) : launch_dma_m<NCB, R, CC, false, 1, EPI_EMASK>(a, p, st);
+        if (p.epi == EPI_BITS_OUT && !m) return launch_dma_m<NCB, R, CC, false, 1, EPI_BITS_OUT>(a, p, st);
+        if (p.epi == EPI_POOL && !m) return launch_dma_m<NCB, R, CC, false, 1, EPI_POOL>(a, p, st);
+        if constexpr (NCB == 2 || NCB == 4) {
+            if (p.epi == EPI_ADD && !m) return launch_dma_m<NCB, R, CC, false, 1, EPI_ADD>(a, p, st);
         }
     }
-    return a.mask ? launch_dma_m<NCB, R, CC, true, true, FOLD>(a, st) : launch_dma_m<NCB, R, CC, false, true, FOLD>(a, st);
+    if (p.epi == EPI_PLAIN) return m ? launch_dma_m<NCB, R, CC, true, FOLD, EPI_PLAIN>(a, p, st) : launch_dma_m<NCB, R, CC, false, FOLD, EPI_PLAIN>(a, p, st);
+    ynet_set_error("conv2d: no LDS-DMA kernel for tiles=%d rows=%d fold=%d with epilogue %d%s", NCB, R, FOLD, p.epi, m ? " and a mask" : "");
+    return 1;
 }
 
-// The small tiles: the deepest chunk (8 / 16 / 32 input channels, YNET_CONV_SMALL_CC caps it) whose double buffer fits the LDS --
-// two resident workgroups per CU for the two-row tiles of the 32^2 / 64^2 maps (<= 72 KB), one for the folded 8^2 / 16^2 tiles
-// (their launches have at most one workgroup per CU anyway) -- so that a 64-channel layer is 2-4 DMA round trips instead of 8;
-// the variants with an epilogue extra (output mask, pooled copy, bit masks) keep 8.
-template <int NCB, int R, int FOLD = 1>
-static int launch_dma_small(ConvArgs& a, hipStream_t st) {
-    const int cc = small_cc();
-    // (one-row / folded tiles have no epilogue variants: an output mask is applied by the split reduction or a pass of its own, so
-    // the launch is the plain kernel whatever the caller asked for -- and a masked call must sum in the same order as a plain one)
-    const bool plain = !(R >= 2 && FOLD == 1) || (!a.emask && !a.pool && !a.bits_out && !a.bits_in);
-    constexpr int budget = (R >= 2 && FOLD == 1) ? 72 * 1024 : 152 * 1024;
-    if constexpr (DmaCfg<NCB, R, 32, false, true, FOLD>::LDS_BYTES <= budget) {
-        if (plain && cc >= 32 && a.cin > 16)
-            return a.mask ? launch_dma_m<NCB, R, 32, true, true, FOLD>(a, st) : launch_dma_m<NCB, R, 32, false, true, FOLD>(a, st);
-    }
-    if constexpr (DmaCfg<NCB, R, 16, false, true, FOLD>::LDS_BYTES <= budget) {
-        if (plain && cc >= 16 && a.cin > 8)
-            return a.mask ? launch_dma_m<NCB, R, 16, true, true, FOLD>(a, st) : launch_dma_m<NCB, R, 16, false, true, FOLD>(a, st);
-    }
-    if (cc >= 8) return launch_dma<NCB, R, FOLD, 8>(a, st);
-    return launch_dma<NCB, R, FOLD, 4>(a, st);
-}
-
-// Host mirror of launch_dma_small's choice for a PLAIN launch with `cin` input channels (ynet_conv2d_plan).
-static int small_chunk_depth(int ncb, int rows, int fold, int cin) {
-    const int tw = 32 / fold, th = 4 * rows * fold, plane = (th + 2) * (tw + 8);
-    const int chs = plane + (fold == 4 ? ((8 - plane % 32) + 32) % 32 : 0);
-    const int budget = (rows >= 2 && fold == 1) ? 72 * 1024 : 152 * 1024;
-    const int cap = small_cc();
-    for (int cc = 32; cc >= 16; cc >>= 1)
-        if (cap >= cc && cin > cc / 2 && 2 * cc * (chs + 9 * 16 * ncb) * 4 <= budget) return cc;
-    return cap >= 8 ? 8 : 4;
-}
-
-// Large maps: rows >= 2 per wave (R = 4 only up to 32 output channels per workgroup: registers).
-template <int NCB>
-static int launch_dma_r(ConvArgs& a, hipStream_t st, int rows) {
-    if (rows == 4) {
-        if constexpr (NCB < 3) return launch_dma<NCB, 4>(a, st);
-    }
-    if (rows == 3) {
-        if constexpr (NCB == 2) return launch_dma<NCB, 3>(a, st);
-    }
-    if (rows >= 2) {
-        if constexpr (NCB <= 2) return NCB == 1 ? launch_dma_small<NCB, 2>(a, st) : launch_dma<NCB, 2>(a, st);
-        else return launch_dma<NCB, 2>(a, st);
-    }
-    if constexpr (NCB <= 2) return launch_dma_small<NCB, 1>(a, st);
-    else return launch_dma<NCB, 1>(a, st);
-}
-
-// Maps no wider than 16 / 8 pixels: folded row units, one per wave
-template <int NCB>
-static int launch_dma_fold(ConvArgs& a, hipStream_t st, int fold) {
-    if constexpr (NCB <= 2) return fold == 4 ? launch_dma_small<NCB, 1, 4>(a, st) : launch_dma_small<NCB, 1, 2>(a, st);
-    else return fold == 4 ? launch_dma<NCB, 1, 4>(a, st) : launch_dma<NCB, 1, 2>(a, st);
-}
-
-template <int KS, int NCB, int CC, bool M16 = false>
-static int launch_conv_r(ConvArgs& a, hipStream_t st) {
-    int rows = pick_rows(a, (M16 ? 16 : 32) * NCB);
-    if (M16 && NCB >= 3 && rows == 4) rows = 2;      // 3-4 tiles x 4 rows x 2 halves would spill (> 256 VGPRs)
-    switch (rows) {
-        case 4: if constexpr (!(M16 && NCB >= 3)) return launch_conv<KS, NCB, 4, CC, M16>(a, st);
-        case 2: return launch_conv<KS, NCB, 2, CC, M16>(a, st);
-        default: return launch_conv<KS, NCB, 1, CC, M16>(a, st);
-    }
+static int launch_plan_dma(ConvArgs& a, const DirectPlan& p, hipStream_t st) {
+#define DMA_CASE(NCB, R, CC, FOLD) \
+    if (p.tiles == NCB && p.rows == R && p.cc == CC && p.fold == FOLD) return launch_dma<NCB, R, CC, FOLD>(a, p, st)
+    DMA_CASE(1, 4, 4, 1); DMA_CASE(1, 2, 8, 1);
+    DMA_CASE(2, 4, 4, 1); DMA_CASE(2, 2, 4, 1);
+    DMA_CASE(3, 2, 4, 1);
+    DMA_CASE(4, 2, 4, 1);
+    DMA_CASE(1, 1, 8, 2); DMA_CASE(1, 1, 8, 4);
+    DMA_CASE(2, 1, 8, 2); DMA_CASE(2, 1, 8, 4);
+    DMA_CASE(3, 1, 4, 2); DMA_CASE(3, 1, 4, 4);
+    DMA_CASE(4, 1, 4, 2); DMA_CASE(4, 1, 4, 4);
+#undef DMA_CASE
+    ynet_set_error("conv2d: no LDS-DMA kernel for tiles=%d rows=%d chunk=%d fold=%d", p.tiles, p.rows, p.cc, p.fold);
+    return 1;
 }
 
 
@@ -1611,95 +1645,16 @@ static int launch_conv1x1_stream(const ConvArgs& a, hipStream_t st) {
     return ynet_check_launch("conv2d(1x1)");
 }
 
-// 16-wide output-channel tiles pay off when padding Cout to 32 / 64 would waste a quarter or more
-static int m16_tiles(int K, int cout) {
-    static const int mode = getenv("YNET_CONV_M16") ? atoi(getenv("YNET_CONV_M16")) : 2;   // 0 off, 1 only where 32-wide tiles would pad, 2 always for 3x3 (2-6 % faster on MI355X)
-    if (mode == 0 || K != 3) return 0;
-    if (cout <= 16) return 1;
-    if (cout > 32 && cout <= 48) return 3;
-    if (mode == 2) return cout <= 32 ? 2 : 4;
-    return 0;
-}
-
-static int conv_fold(int H, int W) {
-    static const int on = getenv("YNET_CONV_FOLD") ? atoi(getenv("YNET_CONV_FOLD")) : 1;
-    if (!on) return 1;
-    if (W <= 8 && (H & 3) == 0) return 4;
-    if (W <= 16 && (H & 1) == 0) return 2;
+static int conv_dispatch_kernels(ConvArgs& a, const DirectPlan& p, int K, hipStream_t st) {
+    switch (p.gen) {
+        case GEN_DMA:
+        case GEN_FOLD: return launch_plan_dma(a, p, st);
+        case GEN_STREAM: return p.tiles == 1 ? launch_conv1x1_stream<16, 4>(a, st) : launch_conv1x1_stream<32, 2>(a, st);
+        case GEN_REG: return launch_plan_reg(a, p, K, st);
+    }
+    if (a.addend != nullptr) ynet_set_error("conv2d_add: shape B=%d %dx%d cout=%d is not served by the additive-term kernels", a.B, a.H, a.W, a.cout);
+    else ynet_set_error("conv2d: kernel size %d not supported (1, 3, 5)", K);
     return 1;
-}
-
-// Small and mid-size maps: fewer output channels per workgroup -> more workgroups.  A 64 -> 64 layer on B x 32^2 pixels is 256
-// row units: with all 64 output channels in one workgroup that is ONE workgroup per CU (one wave per SIMD, nothing to hide
-// its staging latency behind); 16 channels per workgroup give four per CU and the same MFMA count in total (the input tile
-// is then staged by four workgroups instead of one -- from L2).  Measured on the captured C2 step (MI355X): target 0 / 512 /
-// 1024 / 2048 / 4096 work items -> 9.78 / 9.69 / 9.63 / 9.56 / 9.55 ms at B = 32 and 4.05 / 3.88 / 3.84 / 3.79 / 3.79 ms at the
-// reference scripts' batch of 10; the 16^2 .. 64^2 layers need less (or no) split of the channel loop with it.
-static int narrow_tiles(const ConvArgs& a, int nt16) {
-    static const int target = getenv("YNET_CONV_NARROW") ? atoi(getenv("YNET_CONV_NARROW")) : 2048;   // wanted work items (0: off)
-    if (target <= 0 || nt16 <= 1) return nt16;
-    const int fold = conv_fold(a.H, a.W);
-    const long long units = (long long)a.B * ceil_div(a.W, 32 / fold) * ceil_div(a.H, 4 * fold);      // one-row-per-wave tiles
-    int n = nt16;
-    while (n > 1 && units * ceil_div(nt16, n) < target) n = n > 2 ? 2 : 1;
-    return n;
-}
-
-static int conv_dispatch_kernels(ConvArgs& a, int K, hipStream_t st) {
-    const bool wide = a.cout > 32;
-    const int nt16_full = m16_tiles(K, a.cout);
-    const int nt16 = (a.addend == nullptr) ? narrow_tiles(a, nt16_full) : nt16_full;
-    static const int use_dma = getenv("YNET_CONV_DMA") ? atoi(getenv("YNET_CONV_DMA")) : 1;
-    static const int use_x4 = getenv("YNET_CONV_X4") ? atoi(getenv("YNET_CONV_X4")) : 1;
-    static const int dma_r1 = getenv("YNET_CONV_DMA_R1") ? atoi(getenv("YNET_CONV_DMA_R1")) : 0;      // (round 4: with the flat DMA items the one-row LDS-DMA tile is 1 % faster in the step -- B 10 3.525 -> 3.49 ms, B 32 8.965 -> 8.94 -- but its summation order moves one near-zero filter gradient of the tiny_long_train fixture by 2.4e-7 against a bound of 1.95e-7: off, the parity suite stays at its tolerances)
-    if (a.addend != nullptr) {
-        // the additive term is implemented by the large-map LDS-DMA kernels only (what evaluate()'s shared skip features
-        // need); callers ask ynet_conv2d_add_supported first
-        const int rows_a = (nt16 == 2 || nt16 == 4) ? dma_rows(a, nt16) : 0;
-        const bool ok = use_dma && use_x4 && a.vec_store && a.vec_load && a.mask == nullptr && a.ndst == 1 && conv_fold(a.H, a.W) == 1 &&
-                        rows_a >= 2 && (reinterpret_cast<uintptr_t>(a.addend) & 15) == 0 && (a.addend_bs & 3) == 0;
-        if (!ok) {
-            ynet_set_error("conv2d_add: shape B=%d %dx%d cout=%d is not served by the additive-term kernels", a.B, a.H, a.W, a.cout);
-            return 1;
-        }
-        if (nt16 == 2) return rows_a == 4 ? launch_dma_m<2, 4, 4, false, true, 1, 1>(a, st) :
-                              (rows_a == 3 ? launch_dma_m<2, 3, 4, false, true, 1, 1>(a, st) : launch_dma_m<2, 2, 4, false, true, 1, 1>(a, st));
-        return launch_dma_m<4, 2, 4, false, true, 1, 1>(a, st);
-    }
-    if (nt16 && use_dma && use_x4 && a.vec_store && a.vec_load) {
-        const int fold = conv_fold(a.H, a.W);
-        if (fold > 1) {
-            switch (nt16) {
-                case 1: return launch_dma_fold<1>(a, st, fold);
-                case 2: return launch_dma_fold<2>(a, st, fold);
-                case 3: return launch_dma_fold<3>(a, st, fold);
-                default: return launch_dma_fold<4>(a, st, fold);
-            }
-        }
-        const int rows = dma_rows(a, nt16);
-        if (rows >= 2 || dma_r1) {
-            switch (nt16) {
-                case 1: return launch_dma_r<1>(a, st, rows);
-                case 2: return launch_dma_r<2>(a, st, rows);
-                case 3: return launch_dma_r<3>(a, st, rows);
-                default: return launch_dma_r<4>(a, st, rows);
-            }
-        }
-    }
-    static const int stream1 = getenv("YNET_CONV_1X1_STREAM") ? atoi(getenv("YNET_CONV_1X1_STREAM")) : 1;
-    if (K == 1 && stream1 && a.nsrc == 1 && a.ndst == 1 && a.dst[0].p != nullptr && a.mask == nullptr && a.cout <= 32 &&
-        a.src[0].bmod == 0 && a.vec_store && a.vec_load && ((long long)a.H * a.W) % 4 == 0)
-        return a.cout <= 16 ? launch_conv1x1_stream<16, 4>(a, st) : launch_conv1x1_stream<32, 2>(a, st);
-    if (nt16 == 1) return launch_conv_r<3, 1, 8, true>(a, st);
-    if (nt16 == 2) return launch_conv_r<3, 2, 8, true>(a, st);
-    if (nt16 == 3) return launch_conv_r<3, 3, 8, true>(a, st);
-    if (nt16 == 4) return launch_conv_r<3, 4, 8, true>(a, st);
-    switch (K) {
-        case 1: return wide ? launch_conv_r<1, 2, 16>(a, st) : launch_conv_r<1, 1, 16>(a, st);
-        case 3: return wide ? launch_conv_r<3, 2, 8>(a, st) : launch_conv_r<3, 1, YNET_CC_NARROW>(a, st);
-        case 5: return wide ? launch_conv<5, 2, 4, 4>(a, st) : launch_conv<5, 1, 4, 4>(a, st);
-        default: ynet_set_error("conv2d: kernel size %d not supported (1, 3, 5)", K); return 1;
-    }
 }
 
 // dst = emask > 0 ? dst : 0 for the kernel families without the output-side mask in their epilogue (register-staged tiles,
@@ -1713,18 +1668,31 @@ __global__ __launch_bounds__(256) void conv_emask_kernel(float* __restrict__ dst
 }
 
 static int conv_dispatch(ConvArgs& a, int K, hipStream_t st) {
-    a.emask_done = 0;
-    a.pool_done = 0;
-    a.bits_done = 0;
-    int rc = conv_dispatch_kernels(a, K, st);
-    if (!rc && (a.bits_out != nullptr || a.bits_in != nullptr) && !a.bits_done) {
+    DirectCall c{};
+    c.B = a.B, c.H = a.H, c.W = a.W, c.cout = a.cout, c.K = K;
+    c.vec_load = a.vec_load != 0;
+    c.vec_store = a.vec_store != 0;
+    c.mask = a.mask != nullptr;
+    c.emask = a.emask != nullptr;
+    c.pool = a.pool != nullptr;
+    c.bits_out = a.bits_out != nullptr;
+    c.bits_in = a.bits_in != nullptr;
+    c.addend = a.addend != nullptr;
+    c.addend_ok = a.ndst == 1 && (reinterpret_cast<uintptr_t>(a.addend) & 15) == 0 && (a.addend_bs & 3) == 0;
+    c.stream_ok = a.nsrc == 1 && a.ndst == 1 && a.dst[0].p != nullptr && a.src[0].bmod == 0;
+    const DirectPlan p = make_direct_plan(c);
+    // The 1-bit masks and the pooled copy exist in the epilogues of the unfolded LDS-DMA tiles only: a plan without them is refused
+    // before anything is launched.
+    if ((c.bits_out || c.bits_in) && p.epi != EPI_BITS_OUT && p.epi != EPI_BITS_IN) {
         ynet_set_error("conv2d (bit mask): shape B=%d %dx%d cout=%d is not served by the bit-mask epilogues (ask ynet_conv2d_relu_bits_words)", a.B, a.H, a.W, a.cout);
         return 1;
     }
-    if (!rc && a.pool != nullptr && !a.pool_done) {
+    if (c.pool && p.epi != EPI_POOL) {
         ynet_set_error("conv2d_pool: shape B=%d %dx%d cout=%d is not served by the pooling epilogue (ask ynet_conv2d_pool_supported)", a.B, a.H, a.W, a.cout);
         return 1;
     }
+    a.emask_done = 0;
+    const int rc = conv_dispatch_kernels(a, p, K, st);
     if (rc || a.emask == nullptr || a.emask_done) return rc;
     const long long per_image = (long long)a.cout * a.H * a.W, total = per_image * a.B;
     long long blocks = (total + 255) / 256;
@@ -1761,36 +1729,25 @@ __global__ void pack_weight_kernel(const float* __restrict__ w, float* __restric
 
 extern "C" {
 
+// The plan of a plain call of this shape on 16-byte aligned operands (W % 4 != 0: no operand is aligned), or of such a call with an
+// additive term: what the shape queries below read.  It leaves the 1x1 streaming kernel out (its gates are on the operands), so a
+// 1x1 shape names the tile kernel that an unaligned call takes.
+static DirectPlan shape_plan(int B, int H, int W, int cout, int K, bool addend = false) {
+    DirectCall c{};
+    c.B = B, c.H = H, c.W = W, c.cout = cout, c.K = K;
+    c.vec_load = c.vec_store = (W % 4) == 0;
+    c.addend = c.addend_ok = addend;
+    return make_direct_plan(c);
+}
+
 // The kernel instantiation the dispatcher picks for this problem, for naming it in profiles:
 // returns rows | tiles << 8 | m16 << 16 | dma << 17 | x4 << 18 | log2(fold) << 19 | CC << 21
 //   ->  conv_mfma_kernel<K, tiles, rows, CC, mask, m16> or, with dma, conv_dma_kernel<tiles, rows, CC, mask, x4, fold>
-//   (CC of a 16-channel-chunk small tile drops to 8 for a masked / output-masked / pooled launch).
 int ynet_conv2d_plan(int B, int H, int W, int cout, int K) {
-    ConvArgs a{};
-    a.B = B;
-    a.H = H;
-    a.W = W;
-    a.cout = cout;
-    const int nt16 = narrow_tiles(a, m16_tiles(K, cout));
-    const int tiles = nt16 ? nt16 : (cout > 32 ? 2 : 1);
-    static const int use_dma = getenv("YNET_CONV_DMA") ? atoi(getenv("YNET_CONV_DMA")) : 1;
-    static const int use_x4 = getenv("YNET_CONV_X4") ? atoi(getenv("YNET_CONV_X4")) : 1;      // 16-byte input DMA (aligned planes assumed)
-    int rows = K == 5 ? 4 : pick_rows(a, nt16 ? 16 * nt16 : 32 * tiles);
-    if (nt16 >= 3 && rows == 4) rows = 2;
-    if (nt16 && use_dma && use_x4 && (W % 4) == 0 && conv_fold(H, W) == 1) rows = dma_rows(a, nt16);      // (a pooled launch of the two-tile kernel keeps 4 rows)
-    static const int dma_r1 = getenv("YNET_CONV_DMA_R1") ? atoi(getenv("YNET_CONV_DMA_R1")) : 0;      // (round 4: with the flat DMA items the one-row LDS-DMA tile is 1 % faster in the step -- B 10 3.525 -> 3.49 ms, B 32 8.965 -> 8.94 -- but its summation order moves one near-zero filter gradient of the tiny_long_train fixture by 2.4e-7 against a bound of 1.95e-7: off, the parity suite stays at its tolerances)
-    const bool can = nt16 && use_dma && use_x4 && (W % 4) == 0;
-    const int fold = can ? conv_fold(H, W) : 1;
-    if (fold > 1) rows = 1;
-    const int dma = (can && (fold > 1 || rows >= 2 || dma_r1)) ? 1 : 0;
-    const int flog = fold == 4 ? 2 : (fold == 2 ? 1 : 0);
-    // input channels per staged chunk (the CC template argument): the small tiles of launch_dma_small take deeper chunks
-    int cc = K == 1 ? 16 : (K == 5 ? 4 : 8);
-    if (dma) {
-        const bool small = nt16 <= 2 && (fold > 1 || rows == 1 || (rows == 2 && nt16 == 1));
-        cc = small ? small_chunk_depth(nt16, rows, fold, 1 << 30) : 4;
-    }
-    return rows | (tiles << 8) | ((nt16 ? 1 : 0) << 16) | (dma << 17) | (dma << 18) | (flog << 19) | (cc << 21);
+    const DirectPlan p = shape_plan(B, H, W, cout, K);
+    const int dma = (p.gen == GEN_DMA || p.gen == GEN_FOLD) ? 1 : 0;
+    const int flog = p.fold == 4 ? 2 : (p.fold == 2 ? 1 : 0);
+    return p.rows | (p.tiles << 8) | ((p.nt16 ? 1 : 0) << 16) | (dma << 17) | (dma << 18) | (flog << 19) | (p.cc << 21);
 }
 
 long long ynet_packed_weight_floats(int cout, int cin, int K, int mode) {
@@ -1901,7 +1858,7 @@ static int conv2d_impl(const float* const* src, const int* src_c, const long lon
     if (mask && ((reinterpret_cast<uintptr_t>(mask) & 15) || (mask_bs & 3))) a.vec_load = 0;
     if ((W % 4) == 0 && (pool != nullptr || bits_out != nullptr || bits_in != nullptr || addend != nullptr)) {
         // The pooled copy, the 1-bit masks and the additive term exist in the LDS-DMA kernels only.  An operand off a 16-byte boundary would
-        // send the call to the register-staged tiles, which write dst and only then find the epilogue missing: refuse it HERE, before any launch.
+        // send the call to the register-staged tiles, which have no such epilogue: say which operand it is.
         const char* what = pool ? "conv2d_pool" : (addend ? "conv2d_add" : "conv2d (bit mask)");
         for (int i = 0; i < a.nsrc; ++i)
             YNET_REQUIRE(!(reinterpret_cast<uintptr_t>(a.src[i].p) & 15) && !(a.src[i].bs & 3),
@@ -1941,25 +1898,16 @@ int ynet_conv2d_dgrad_relu(const float* dy, int dy_c, long long dy_bs, const flo
                        nullptr, 0, 0, stream, relu_of, relu_of_bs);
 }
 
-static int conv_rows_tiles_ok(int B, int H, int W, int cout, int K);
-
 // Words (uint32) of the 1-bit activation mask a ReLU convolution with this OUTPUT shape writes next to its output
 // (ynet_conv2d_relu_bits) and the data gradient of the following convolution applies to ITS output, which has that same
 // shape (ynet_conv2d_dgrad_relu_bits); 0: this shape is not served (then ynet_conv2d + ynet_conv2d_dgrad_relu with the float
 // activation).  Both launches tile the [B, cout, H, W] tensor identically (the tiling is a function of B, H, W, cout, K only),
 // and the mask lives in the register layout of those tiles: [tile][256 lanes][ceil(tiles * rows * 8 / 32)].
 long long ynet_conv2d_relu_bits_words(int B, int H, int W, int cout, int K) {
-    static const int on = getenv("YNET_RELU_BITS") ? atoi(getenv("YNET_RELU_BITS")) : 1;
-    if (!on || !conv_rows_tiles_ok(B, H, W, cout, K)) return 0;
-    ConvArgs a{};
-    a.B = B;
-    a.H = H;
-    a.W = W;
-    a.cout = cout;
-    const int nt16 = narrow_tiles(a, m16_tiles(K, cout));
-    const int rows = dma_rows(a, nt16);
-    const long long tiles = (long long)ceil_div(W, 32) * ceil_div(H, 4 * rows) * ceil_div(cout, 16 * nt16) * B;
-    return tiles * 256 * ((nt16 * rows * 8 + 31) / 32);
+    const DirectPlan p = shape_plan(B, H, W, cout, K);
+    if (!conv_gates().relu_bits || p.gen != GEN_DMA) return 0;
+    const long long tiles = (long long)ceil_div(W, 32) * ceil_div(H, 4 * p.rows) * ceil_div(cout, p.cb) * B;
+    return tiles * 256 * ((p.tiles * p.rows * 8 + 31) / 32);
 }
 
 // relu(conv(cat(src...), wp) + bias) -> dst, and the 1-bit mask (dst > 0) -> bits [ynet_conv2d_relu_bits_words(...)]
@@ -1993,30 +1941,15 @@ int ynet_conv2d_dgrad_relu_bits(const float* dy, int dy_c, long long dy_bs, cons
 // ynet_conv2d with one destination + its 2 x 2 max-pooled copy (MaxPool2d(2, 2) of the next encoder stage, models/ynet.py:202,215)
 // written by the same epilogue.  ynet_conv2d_pool_supported: the shapes that take it (3x3, two-row tiles: the large maps, where the
 // stand-alone pool is a 60 us pass on the forward's critical path).
-static int conv_rows_tiles_ok(int B, int H, int W, int cout, int K) {
-    ConvArgs a{};
-    a.B = B;
-    a.H = H;
-    a.W = W;
-    a.cout = cout;
-    const int nt16 = narrow_tiles(a, m16_tiles(K, cout));
-    static const int use_dma = getenv("YNET_CONV_DMA") ? atoi(getenv("YNET_CONV_DMA")) : 1;
-    static const int use_x4 = getenv("YNET_CONV_X4") ? atoi(getenv("YNET_CONV_X4")) : 1;
-    if (!(use_dma && use_x4) || K != 3 || (W & 3) || nt16 == 0 || conv_fold(H, W) != 1) return 0;
-    const int rows = dma_rows(a, nt16);
-    return rows >= 2 ? 1 : 0;
-}
-
 int ynet_conv2d_pool_supported(int B, int H, int W, int cout, int K) {
-    return ((H | W) & 1) == 0 && conv_rows_tiles_ok(B, H, W, cout, K);
+    return ((H | W) & 1) == 0 && shape_plan(B, H, W, cout, K).gen == GEN_DMA;
 }
 
 int ynet_conv2d_pool(const float* const* src, const int* src_c, const long long* src_bs, int nsrc, const float* wp, const float* bias,
                      float* dst, int cout, long long dst_bs, float* pooled, long long pooled_bs,
                      int B, int H, int W, int K, int relu, void* stream) {
     YNET_REQUIRE(dst != nullptr && pooled != nullptr, "conv2d_pool: null destination");
-    // (refused HERE, before anything is launched: outside these shapes conv_dispatch would run the plain kernel, which writes dst, and only
-    //  then find the pooled copy missing -- its check stays as a backstop)
+    // (refused before anything is launched; conv_dispatch holds the plan of the actual call, operand alignment included, to the same rule)
     YNET_REQUIRE(ynet_conv2d_pool_supported(B, H, W, cout, K), "conv2d_pool: shape B=%d %dx%d cout=%d is not served by the pooling epilogue (ask ynet_conv2d_pool_supported)", B, H, W, cout);
     float* dsts[1] = {dst};
     const int dc[1] = {cout};
@@ -2028,31 +1961,12 @@ int ynet_conv2d_pool(const float* const* src, const int* src_c, const long long*
 // 1 if ynet_conv2d_dgrad_relu applies the mask inside the convolution kernel for this problem (3x3 on a map large enough for
 // two-row units); elsewhere it is still correct but adds a pass over dx -- callers keep the consumer-side mask there
 int ynet_conv2d_dgrad_relu_supported(int B, int H, int W, int dx_c, int K) {
-    ConvArgs a{};
-    a.B = B;
-    a.H = H;
-    a.W = W;
-    a.cout = dx_c;
-    const int nt16 = narrow_tiles(a, m16_tiles(K, dx_c));
-    static const int use_dma = getenv("YNET_CONV_DMA") ? atoi(getenv("YNET_CONV_DMA")) : 1;
-    static const int use_x4 = getenv("YNET_CONV_X4") ? atoi(getenv("YNET_CONV_X4")) : 1;
-    if (!(use_dma && use_x4) || K != 3 || (W & 3) || nt16 == 0 || conv_fold(H, W) != 1) return 0;
-    const int rows = dma_rows(a, nt16);
-    return rows >= 2 ? 1 : 0;
+    return shape_plan(B, H, W, dx_c, K).gen == GEN_DMA;
 }
 
 // 1 if ynet_conv2d_add serves this problem (3x3, Cout 17..32 or 49..64, W % 4 == 0, a map large enough for two-row units)
 int ynet_conv2d_add_supported(int B, int H, int W, int cout, int K) {
-    ConvArgs a{};
-    a.B = B;
-    a.H = H;
-    a.W = W;
-    a.cout = cout;
-    const int nt16 = m16_tiles(K, cout);
-    static const int use_dma = getenv("YNET_CONV_DMA") ? atoi(getenv("YNET_CONV_DMA")) : 1;
-    static const int use_x4 = getenv("YNET_CONV_X4") ? atoi(getenv("YNET_CONV_X4")) : 1;
-    if (!(use_dma && use_x4) || K != 3 || (W & 3) || (nt16 != 2 && nt16 != 4) || conv_fold(H, W) != 1) return 0;
-    return dma_rows(a, nt16) >= 2 ? 1 : 0;
+    return shape_plan(B, H, W, cout, K, true).gen == GEN_DMA;
 }
 
 // y = [relu](conv(cat(src...), wp) + bias + addend[b % addend_bmod]): ynet_conv2d with one destination, no mask, plus a

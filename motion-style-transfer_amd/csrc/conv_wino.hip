@@ -1446,15 +1446,38 @@ __global__ void wino_filter_kernel(const float* __restrict__ wp, f32x4* __restri
 // The packed filter's column padding (conv_mfma.hip: YNET_COUT_PAD)
 static int wino_cols_pad(int cols) { return ceil_div(cols, 64) * 64; }
 
+// The development switches of the Winograd dispatch (A/B measurements only), read from the environment once per process.
+struct WinoGates {
+    int on;             // YNET_WINOGRAD: every Winograd form
+    int on48;           // YNET_WINOGRAD48: 48 outputs (three blocks per wave, one wave per SIMD -- the two-destination data gradient)
+    int cat;            // YNET_WINOGRAD_CAT: the concatenating form (conv_wino_cat_kernel)
+    int on16;           // YNET_WINOGRAD16: the slice form (conv_wino16_kernel)
+    int up;             // YNET_WINOGRAD_UP: the up-convolution forms
+    int min_pixels;     // YNET_WINOGRAD_MIN: B H W from which the plain, concatenating and up-convolution forms serve (one workgroup of eight waves per CU: small launches stay with the
+                        // direct tiles; round 4: 16 -> 8 images of 128^2 -- batch 10 at 128^2 is 320 tiles: 3.15 -> 3.00 ms per step there, nothing lost at batch 32)
+    int min_pixels16;   // YNET_WINOGRAD16_MIN (not set: YNET_WINOGRAD_MIN): the same for the slice forms (40 K pixels: batch 10 at 64^2 is served -- 3.02 -> 2.92 ms
+                        // per step there --, batch 32 at 32^2 is not: one 8-unit tile per workgroup on half the CUs takes 30-37 us per launch where the direct
+                        // tiles take 27-30, and the 96 / 97-channel layers would be two launches)
+    int w12;            // YNET_WINOGRAD_W12: twelve waves per workgroup for the 16-output kernel (launch_wino)
+    int pred_bce;       // YNET_CONV_PRED_BCE: the predictor + loss epilogue (ynet_conv2d_winograd_pred_bce_supported)
+};
+
+static const WinoGates& wino_gates() {
+    static const WinoGates g = {ynet_env_int("YNET_WINOGRAD", 1),     ynet_env_int("YNET_WINOGRAD48", 1),
+                                ynet_env_int("YNET_WINOGRAD_CAT", 1), ynet_env_int("YNET_WINOGRAD16", 1),
+                                ynet_env_int("YNET_WINOGRAD_UP", 1),  ynet_env_int("YNET_WINOGRAD_MIN", 128 * 128 * 8),
+                                ynet_env_int("YNET_WINOGRAD16_MIN", ynet_env_int("YNET_WINOGRAD_MIN", 64 * 64 * 10)),
+                                ynet_env_int("YNET_WINOGRAD_W12", 0), ynet_env_int("YNET_CONV_PRED_BCE", 1)};
+    return g;
+}
+
 static bool wino_shape_ok(int B, int H, int W, int cin, int cout, int K) {
-    static const int on = getenv("YNET_WINOGRAD") ? atoi(getenv("YNET_WINOGRAD")) : 1;
-    if (!on || K != 3 || B <= 0) return false;
+    const WinoGates& g = wino_gates();
+    if (!g.on || K != 3 || B <= 0) return false;
     if (H % WN_TH || W % WN_TW || H < WN_TH || W < WN_TW) return false;
-    static const int on48 = getenv("YNET_WINOGRAD48") ? atoi(getenv("YNET_WINOGRAD48")) : 1;      // (48 outputs: three blocks per wave, one wave per SIMD -- the two-destination data gradient)
-    if ((cin != 16 && cin != 32) || (cout != 16 && cout != 32 && !(cout == 48 && on48))) return false;
+    if ((cin != 16 && cin != 32) || (cout != 16 && cout != 32 && !(cout == 48 && g.on48))) return false;
     if (48ll * H * W * 4 + (W + 4) * 4 >= (1ll << 31)) return false;      // one image per buffer descriptor, below 2 GB (the batch is unbounded)
-    static const int min_pixels = getenv("YNET_WINOGRAD_MIN") ? atoi(getenv("YNET_WINOGRAD_MIN")) : 128 * 128 * 8;      // (round 4: 16 -> 8 -- batch 10 at 128^2 is 320 tiles: 3.15 -> 3.00 ms per step there, nothing lost at batch 32)
-    return (long long)B * H * W >= min_pixels;      // (one workgroup of eight waves per CU: small launches stay with the direct tiles)
+    return (long long)B * H * W >= g.min_pixels;
 }
 
 template <int NCB, int NCH, int EM, int NW>
@@ -1486,9 +1509,8 @@ static int launch_wino_nw(WinoArgs& a, hipStream_t st) {
 // pipes' work.  Left as a switch (YNET_WINOGRAD_W12=1).
 template <int NCB, int NCH, int EM>
 static int launch_wino(WinoArgs& a, hipStream_t st) {
-    static const int w12 = getenv("YNET_WINOGRAD_W12") ? atoi(getenv("YNET_WINOGRAD_W12")) : 0;
     if constexpr (NCB == 1) {
-        if (w12) return launch_wino_nw<NCB, NCH, EM, 12>(a, st);
+        if (wino_gates().w12) return launch_wino_nw<NCB, NCH, EM, 12>(a, st);
     }
     return launch_wino_nw<NCB, NCH, EM, 8>(a, st);
 }
@@ -1521,17 +1543,15 @@ static int wino_cat_padded(const int* src_c, int nsrc) {
 }
 
 static bool wino_cat_ok(int B, int H, int W, const int* src_c, int nsrc, int cout, int K) {
-    static const int on = getenv("YNET_WINOGRAD") ? atoi(getenv("YNET_WINOGRAD")) : 1;
-    static const int cat_on = getenv("YNET_WINOGRAD_CAT") ? atoi(getenv("YNET_WINOGRAD_CAT")) : 1;
-    if (!on || !cat_on || K != 3 || B <= 0 || nsrc < 1 || nsrc > WC_MAX_SRC || cout != 32) return false;
+    const WinoGates& g = wino_gates();
+    if (!g.on || !g.cat || K != 3 || B <= 0 || nsrc < 1 || nsrc > WC_MAX_SRC || cout != 32) return false;
     if (H % WN_TH || W % WN_TW || H < WN_TH || W < WN_TW) return false;
     for (int i = 0; i < nsrc; ++i)
         if (src_c[i] <= 0) return false;
     const int nch = wino_cat_padded(src_c, nsrc) / 4;
     if (56ll * H * W * 4 + (W + 4) * 4 >= (1ll << 31)) return false;      // one image of one source per buffer descriptor, below 2 GB
     if (nch < 2 || nch > 14) return false;          // 14 chunks of 8 KB of filters + eight 5 KB rings: 156 KB of LDS
-    static const int min_pixels = getenv("YNET_WINOGRAD_MIN") ? atoi(getenv("YNET_WINOGRAD_MIN")) : 128 * 128 * 8;      // (round 4: 16 -> 8 -- batch 10 at 128^2 is 320 tiles: 3.15 -> 3.00 ms per step there, nothing lost at batch 32)
-    return (long long)B * H * W >= min_pixels;
+    return (long long)B * H * W >= g.min_pixels;
 }
 
 int ynet_conv2d_winograd_cat_supported(int B, int H, int W, const int* src_c, int nsrc, int cout, int K) {
@@ -1705,8 +1725,7 @@ int ynet_conv2d_winograd_s2d(const float* src, long long src_bs, const float* u,
 
 // (the blob table and two ints per target plane live in LDS next to the filters and the staging rings: kernlen^2 + 2 B pred_cout words in what the 160 KB leave)
 int ynet_conv2d_winograd_pred_bce_supported(int B, int H, int W, int cin, int cout, int pred_cout, int kernlen) {
-    static const int on = getenv("YNET_CONV_PRED_BCE") ? atoi(getenv("YNET_CONV_PRED_BCE")) : 1;
-    if (!(on && cin == 32 && cout == 32 && pred_cout >= 1 && pred_cout <= 32 && kernlen >= 1 && wino_shape_ok(B, H, W, cin, cout, 3))) return 0;
+    if (!(wino_gates().pred_bce && cin == 32 && cout == 32 && pred_cout >= 1 && pred_cout <= 32 && kernlen >= 1 && wino_shape_ok(B, H, W, cin, cout, 3))) return 0;
     const long long base = 4ll * 8 * 2 * 64 * 16 + 8ll * WN_RING_BYTES + 16 + 8 * 8 + 16;
     const long long lds = pred_cout <= 16 ? base + 5 * 64 * 16 + ((long long)kernlen * kernlen + 2ll * B * pred_cout) * 4      // one block of tables, the blob in LDS
                                           : base + 10 * 64 * 16 + (long long)kernlen * kernlen * 4 + ((2ll * B * pred_cout * 2 + 15) & ~15ll);      // two blocks, 16-bit positions
@@ -1786,9 +1805,8 @@ int ynet_conv2d_winograd_dgrad_relu(const float* dy, long long dy_bs, const floa
 
 // ---- the slice form (conv_wino16_kernel)
 static bool wino16_ok(int B, int H, int W, const int* src_c, int nsrc, int cout, int K) {
-    static const int on = getenv("YNET_WINOGRAD") ? atoi(getenv("YNET_WINOGRAD")) : 1;
-    static const int on16 = getenv("YNET_WINOGRAD16") ? atoi(getenv("YNET_WINOGRAD16")) : 1;
-    if (!on || !on16 || K != 3 || B <= 0 || nsrc < 1 || nsrc > WC_MAX_SRC) return false;
+    const WinoGates& g = wino_gates();
+    if (!g.on || !g.on16 || K != 3 || B <= 0 || nsrc < 1 || nsrc > WC_MAX_SRC) return false;
     if (cout != 16 && cout != 32 && cout != 64 && cout != 128) return false;      // 1 / 2 / 4 / 8 slices: a divisor of the 32 workgroups of an XCD
     if (H % W6_TH || W % WN_TW || H < W6_TH || W < WN_TW) return false;
     for (int i = 0; i < nsrc; ++i)
@@ -1796,10 +1814,7 @@ static bool wino16_ok(int B, int H, int W, const int* src_c, int nsrc, int cout,
     const int nch = wino_cat_padded(src_c, nsrc) / 4;
     if (nch < 2 || nch > W6_MAX_CHUNKS) return false;      // 21 chunks of 4 KB of filters + eight 9.2 KB rings: 158 KB of LDS
     if (84ll * H * W * 4 + (W + 4) * 4 >= (1ll << 31)) return false;      // one image of one source / of the output per buffer descriptor
-    // (40 K pixels: batch 10 at 64^2 is served -- 3.02 -> 2.92 ms per step there --, batch 32 at 32^2 is not: one 8-unit tile per workgroup on
-    //  half the CUs takes 30-37 us per launch where the direct tiles take 27-30, and the 96 / 97-channel layers would be two launches)
-    static const int min_pixels = getenv("YNET_WINOGRAD16_MIN") ? atoi(getenv("YNET_WINOGRAD16_MIN")) : (getenv("YNET_WINOGRAD_MIN") ? atoi(getenv("YNET_WINOGRAD_MIN")) : 64 * 64 * 10);
-    return (long long)B * H * W >= min_pixels;
+    return (long long)B * H * W >= g.min_pixels16;
 }
 
 extern "C" {
@@ -1905,25 +1920,20 @@ int ynet_conv2d_winograd16(const float* const* src, const int* src_c, const long
 // ---- the up-convolution with its bilinear x2 inside (conv_wino_up_kernel)
 // (the slice form of it: cin a multiple of 4 up to 84, 16 / 32 / 64 outputs, 32-row tiles)
 static bool wino16_up_ok(int B, int H, int W, int cin, int cout, int K) {
-    static const int on = getenv("YNET_WINOGRAD") ? atoi(getenv("YNET_WINOGRAD")) : 1;
-    static const int up_on = getenv("YNET_WINOGRAD_UP") ? atoi(getenv("YNET_WINOGRAD_UP")) : 1;
-    static const int on16 = getenv("YNET_WINOGRAD16") ? atoi(getenv("YNET_WINOGRAD16")) : 1;
-    if (!on || !up_on || !on16 || K != 3 || B <= 0 || cin < 8 || cin % 4 || cin / 4 > W6_MAX_CHUNKS) return false;
+    const WinoGates& g = wino_gates();
+    if (!g.on || !g.up || !g.on16 || K != 3 || B <= 0 || cin < 8 || cin % 4 || cin / 4 > W6_MAX_CHUNKS) return false;
     if (cout != 16 && cout != 32 && cout != 64) return false;
     if (H % W6_TH || W % WN_TW || H < W6_TH || W < WN_TW) return false;
     if (84ll * H * W * 4 + (W + 4) * 4 >= (1ll << 31)) return false;
-    static const int min_pixels = getenv("YNET_WINOGRAD16_MIN") ? atoi(getenv("YNET_WINOGRAD16_MIN")) : (getenv("YNET_WINOGRAD_MIN") ? atoi(getenv("YNET_WINOGRAD_MIN")) : 64 * 64 * 10);
-    return (long long)B * H * W >= min_pixels;
+    return (long long)B * H * W >= g.min_pixels16;
 }
 
 static bool wino_up_ok(int B, int H, int W, int cin, int cout, int K) {
-    static const int on = getenv("YNET_WINOGRAD") ? atoi(getenv("YNET_WINOGRAD")) : 1;
-    static const int up_on = getenv("YNET_WINOGRAD_UP") ? atoi(getenv("YNET_WINOGRAD_UP")) : 1;
-    if (!on || !up_on || K != 3 || B <= 0 || cin != 32 || cout != 16) return false;
+    const WinoGates& g = wino_gates();
+    if (!g.on || !g.up || K != 3 || B <= 0 || cin != 32 || cout != 16) return false;
     if (H % WN_TH || W % WN_TW || H < WN_TH || W < WN_TW) return false;      // (H, W: the UP-SAMPLED size; the input is H / 2 x W / 2)
     if (32ll * H * W * 4 + (W + 4) * 4 >= (1ll << 31)) return false;
-    static const int min_pixels = getenv("YNET_WINOGRAD_MIN") ? atoi(getenv("YNET_WINOGRAD_MIN")) : 128 * 128 * 8;
-    return (long long)B * H * W >= min_pixels;
+    return (long long)B * H * W >= g.min_pixels;
 }
 
 extern "C" {

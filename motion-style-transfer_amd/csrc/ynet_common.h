@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define YNET_MAX_SRC 4
 
@@ -35,6 +36,12 @@ void ynet_note_launch(int which, int code);      // (ynet_conv2d_last_launch: wh
     } while (0)
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// A development switch: the integer value of environment variable `name`, `d` where it is not set.
+static inline int ynet_env_int(const char* name, int d) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : d;
+}
 
 // Per-device launch state (function attributes, resident-workgroup counts) is cached per HIP device: a process
 // that drives several GPUs sets the > 64 KB LDS attribute and sizes its persistent grids on each of them.

@@ -7,9 +7,7 @@ conv_emask_kernel and pack_weight_kernel; conv_dispatch_kernels picks the templa
 claim is written down by hand, `launch_plan` recomputes it from the dispatcher's formulas (copied here as plain Python) and the host test holds the two and ynet_conv2d_plan
 against each other -- and the edges it is there for; EDGES recomputes every edge from those formulas.
 
-The gates are read from the environment once per process: SWITCHES lists them, the host test asserts that none is set.  With the defaults these instantiations are out of
-reach of every call and have no row: R = 3 (YNET_CONV_R3), the one-row LDS-DMA tile conv_dma_kernel<*, 1, *, *, *, 1> (YNET_CONV_DMA_R1), chunk depths 16 and 32 of the
-small tiles (YNET_CONV_SMALL_CC above 8), the 32-wide 3x3 tiles of conv_mfma_kernel (YNET_CONV_M16 0 / 1) and the dword form of the DMA (YNET_CONV_X4 0).
+The gates are read from the environment once per process: SWITCHES lists them, the host test asserts that none is set.
 One gate has no far side at all: the 1x1 streaming kernel wants H W % 4 == 0 next to 16-byte loads, which need W % 4 == 0 -- no shape passes one and fails the other.
 ynet_conv2d_plan does not know the streaming kernel (it names the tile kernel an unaligned 1x1 call takes), so the streaming rows are held to the launch note alone.
 
@@ -34,9 +32,8 @@ LEAD, TRAIL = 2, 1                    # NaN planes around a sliced source
 UNWANTED = 16                         # channels of a destination nobody wants
 CIN_PAD, COUT_PAD = 16, 64            # YNET_CIN_PAD, YNET_COUT_PAD (csrc/conv_mfma.hip)
 SLOTS_MAX = 8 * 256                   # resident workgroups: at most 8 per CU x 256 CUs
-SWITCHES = ["YNET_CONV_R", "YNET_CONV_R3", "YNET_CONV_R4_MIN", "YNET_CONV_R2_MIN", "YNET_CONV_DMA_R1", "YNET_CONV_SMALL_CC", "YNET_CONV_M16", "YNET_CONV_FOLD",
-            "YNET_CONV_NARROW", "YNET_CONV_DMA", "YNET_CONV_X4", "YNET_CONV_1X1_STREAM", "YNET_CONV_NO_KSPLIT", "YNET_KSPLIT_ITEMS", "YNET_KSPLIT_TARGET", "YNET_RELU_BITS",
-            "YNET_CONV_DEBUG"]
+SWITCHES = ["YNET_CONV_R", "YNET_CONV_R4_MIN", "YNET_CONV_R2_MIN", "YNET_CONV_FOLD", "YNET_CONV_NARROW", "YNET_CONV_DMA", "YNET_CONV_1X1_STREAM", "YNET_CONV_NO_KSPLIT",
+            "YNET_KSPLIT_ITEMS", "YNET_KSPLIT_TARGET", "YNET_RELU_BITS", "YNET_CONV_DEBUG"]
 REG, DMA, FOLDED, STREAM = 1, 2, 3, 4      # the kind ynet_conv2d_last_launch(0) reports in bits 0..3
 
 
@@ -102,7 +99,7 @@ def workspace_floats(B, H, W, cout):
 
 
 def rows_tiles_ok(B, H, W, cout, K):
-    """conv_rows_tiles_ok: the unfolded LDS-DMA tiles with two or more rows per wave serve an aligned call of this shape (the epilogue forms live there)."""
+    """make_direct_plan gives GEN_DMA: the unfolded LDS-DMA tiles with two or more rows per wave serve an aligned call of this shape (the epilogue forms live there)."""
     nt16 = narrow_tiles(B, H, W, m16_tiles(K, cout))
     return K == 3 and W % 4 == 0 and nt16 > 0 and conv_fold(H, W) == 1 and dma_rows(B, H, W, cout, nt16) >= 2
 
@@ -142,7 +139,7 @@ def dispatch(B, H, W, cs, cout, K, vl=1, vs=1, ws=0, addend=False, mask=False, e
         else:
             rows = dma_rows(B, H, W, cout, nt16)
             if rows >= 2:
-                kind, tiles, cb, cc = DMA, nt16, 16 * nt16, (8 if rows == 2 and nt16 == 1 else 4)      # (launch_dma_small: the two-row one-tile kernel)
+                kind, tiles, cb, cc = DMA, nt16, 16 * nt16, (8 if rows == 2 and nt16 == 1 else 4)      # (the small tiles take CC 8: the two-row one-tile kernel)
     if kind is None:
         fold = 1
         if K == 1 and stream_ok and len(cs) == 1 and not mask and cout <= 32 and vl and vs and H * W % 4 == 0:
@@ -485,7 +482,7 @@ EDGES = {
     "rows4_one_tile": lambda n: _is(n, entry="conv", kind=DMA, rows=4, tiles=1) and case(n)["cout"] == 16,
     "rows4_two_tiles": lambda n: _is(n, entry="conv", kind=DMA, rows=4, tiles=2) and case(n)["cout"] == 32,
     "rows2_two_tiles": lambda n: _is(n, entry="conv", kind=DMA, rows=2, tiles=2, cc=4),
-    "rows2_one_tile": lambda n: _is(n, entry="conv", kind=DMA, rows=2, tiles=1, cc=8) and case(n)["cout"] == 16,      # (launch_dma_small)
+    "rows2_one_tile": lambda n: _is(n, entry="conv", kind=DMA, rows=2, tiles=1, cc=8) and case(n)["cout"] == 16,      # (a small tile: CC 8)
     "rows2_one_tile_narrowed_from_two": lambda n: _is(n, entry="conv", kind=DMA, rows=2, tiles=1, cc=8, cgroups=2) and case(n)["cout"] == 32,
     "below_rows2_gate": lambda n: _is(n, entry="conv", kind=REG, rows=1) and aligned(case(n)) == (1, 1) and dispatch(case(n)["B"] + 1, case(n)["H"], case(n)["W"], case(n)["cs"], case(n)["cout"], 3)["kind"] == DMA,
     "three_tiles_forced_to_rows2": lambda n: _is(n, kind=DMA, rows=2) and _p(n)["tiles"] >= 3 and _raw_rows(n) == 4 and units(case(n)["B"], case(n)["H"], case(n)["W"]) >= 2048,

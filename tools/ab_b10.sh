@@ -12,7 +12,6 @@ for b in 10 32; do
 run base $b YNET_X=0
 run r2min64 $b YNET_CONV_R2_MIN=64
 run r2min32 $b YNET_CONV_R2_MIN=32
-run r2min64_dmar1 $b YNET_CONV_R2_MIN=64 YNET_CONV_DMA_R1=1
 run r2min64_ks128 $b YNET_CONV_R2_MIN=64 YNET_KSPLIT_ITEMS=128
 run r2min64_ks512 $b YNET_CONV_R2_MIN=64 YNET_KSPLIT_ITEMS=512
 run r2min64_kt1024 $b YNET_CONV_R2_MIN=64 YNET_KSPLIT_TARGET=1024
