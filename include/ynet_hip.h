@@ -760,6 +760,50 @@ int ynet_map_radial(const float* x, long long batch_stride, const float* gt_xy, 
                     int n_rings, float* ring /* [B*C][n_rings] */, float* tail /* [B*C] */, float* mean /* [B*C] */,
                     float* mean_sq /* [B*C] */, int* status, void* stream);
 
+/* Marginals of the goal map: the x- and the y-marginal of the distribution the goals are sampled from -- sigmoid(pred_goal_map /
+ * temperature), every plane normalised (utils/evaluate.py:128-131, utils/image_utils.py:110-135) -- and, against the ground truth, the
+ * per-axis continuous ranked probability score and probability integral transform.  Per plane (b, c) of x [B][C][H][W] (batch stride
+ * `batch_stride` elements, so a channel slice needs no copy), with z = x / T, w = sigmoid(z), f = trunc(w * 2^(s - e)) (s =
+ * YNET_MAP_MARGINALS_FRAC_BITS = 40, e = floor(log2(largest w of the plane)): ynet_map_radial's fixed point, the same code), N = sum f
+ * and g = (rint(gt_x), rint(gt_y)) (half-even; (x, y) = (column, row)):
+ *   col  [B][C][W]    = (sum over the rows of f) / N                  the x-marginal
+ *   row  [B][C][H]    = (sum over the columns of f) / N               the y-marginal
+ *   crps [B][C][2]    (x, y) = sum_{t < g} F(t)^2 + sum_{t >= g} (1 - F(t))^2 over ALL integers t, with F(t) = cum(t) / N the
+ *                     marginal's CDF on the pixel grid (unit spacing): 0 below the map, 1 from its last column / row on.  In map
+ *                     pixels; |a - g| for a point forecast at a; = E|X - g| - E|X - X'| / 2.
+ *   pit  [B][C][2][2] (axis; lower, upper) = F(g - 1), F(g): the two ends of the probability the discrete marginal puts at g; (0, 0)
+ *                     or (1, 1) when g lies off the map on that side.
+ * g need NOT lie inside the map: outside it every term of the sums above is 0 or 1, so a ground truth k pixels outside the map adds
+ * exactly k to the CRPS of the ground truth on the border pixel it left the map through.  Up to YNET_MAP_MARGINALS_GT_MARGIN pixels
+ * outside, it is scored and raises nothing.
+ * One launch, one 256-thread workgroup per plane, the plane read from HBM once and once more through the caches.  w is fp32, formed
+ * exactly as ynet_map_likelihood forms it.  Arithmetic: the column and row sums are sums of 64-bit INTEGERS (added with integer
+ * LDS atomics), cum is their integer prefix sum, and all are divided by the integer total N: each marginal sums to 1 up to
+ * the roundings of the stored fp32 values, and pit upper of the last bin is exactly 1.  Truncation drops less than 2^(e - s) <=
+ * 2^-s * Z per pixel, so a share and a CDF value move by less than n * 2^-s / (1 - n * 2^-s) < n * 2^-39 (n = H * W: 2^-21 at
+ * 512 x 512, 2^-23 at 256 x 256), and the CRPS, whose at most `side` in-map terms each move by less than twice that (d(F^2) <= 2 dF),
+ * by less than 2 * side * n * 2^-39.  Every scaled w is below 2^(s + 1), so n <= YNET_MAP_MARGINALS_MAX_PIXELS = 2^22 keeps a sum
+ * below 2^63.  The squares of the CRPS are summed in fp64, per thread over its consecutive bins and combined in a fixed order.  No
+ * floating-point atomic anywhere: two runs give the same bits, and a plane gives the same col, row and pit bits whichever way it is
+ * read -- in 16-byte vectors where it starts on a 16-byte boundary and holds a multiple of 4 pixels, element by element
+ * otherwise (decided per plane).
+ * YNET_MAP_MARGINALS_MAX_SIDE = 2048: the two integer arrays take 8 * (H + W) <= 32 KB of LDS, five workgroups per compute unit.
+ * Rules: a NaN logit makes every output of its plane NaN; a -inf logit adds 0; +inf is weight 1; sigmoids below fp32's normal range
+ * count as 0; Z == 0 makes every output NaN.  A ground truth that is NaN or infinite, or rounds to more than
+ * YNET_MAP_MARGINALS_GT_MARGIN pixels outside the map on either axis: crps and pit NaN for that plane and *status (device int, zero
+ * it first) becomes 1; col and row stay valid (they do not need g).  Any of col / row / crps / pit may be NULL, not all four; gt_xy
+ * and status may be NULL when neither crps nor pit is asked for (gt_xy is then not read: the same col and row bits either way).
+ * Refused (non-zero, ynet_last_error) before any launch: null x; no output; crps or pit with null gt_xy or null status;
+ * temperature <= 0, not finite, or below 2.95e-39 (where 1 / T is not); B, C, H or W < 1; H or W > YNET_MAP_MARGINALS_MAX_SIDE;
+ * H * W > YNET_MAP_MARGINALS_MAX_PIXELS; batch_stride < C * H * W; B * C >= 2^31. */
+#define YNET_MAP_MARGINALS_FRAC_BITS 40
+#define YNET_MAP_MARGINALS_MAX_PIXELS 4194304
+#define YNET_MAP_MARGINALS_MAX_SIDE 2048
+#define YNET_MAP_MARGINALS_GT_MARGIN 16384
+int ynet_map_marginals(const float* x, long long batch_stride, const float* gt_xy /* may be NULL */, long long B, int C, int H, int W,
+                       float temperature, float* col /* [B*C][W] */, float* row /* [B*C][H] */, float* crps /* [B*C][2] */,
+                       float* pit /* [B*C][2][2] */, int* status, void* stream);
+
 /* ---- heat-map construction -------------------------------------------------------------------- */
 /* get_patch + torch.stack (utils/image_utils.py:40-63; utils/train_epoch.py:63-78;
  * utils/evaluate.py:112-114,250-253): out[n] = tmpl[SH/2 - ry : +H, SW/2 - rx : +W] with

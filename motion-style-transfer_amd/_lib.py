@@ -148,6 +148,7 @@ SIGNATURES = {
     "ynet_map_occupancy_workspace_bytes": (c_ll, [c_ll, c_i, c_i, c_i, c_ll, c_i]),
     "ynet_map_occupancy": (c_i, [c_fp, c_ll, c_fp, c_ll, c_ll, c_i, c_i, c_i, c_i, c_f, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "ynet_map_radial": (c_i, [c_fp, c_ll, c_fp, c_ll, c_i, c_i, c_i, c_f, c_i, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "ynet_map_marginals": (c_i, [c_fp, c_ll, c_fp, c_ll, c_i, c_i, c_i, c_f, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "ynet_pad2d":(c_i, [c_fp, c_fp, c_ll, c_i, c_i, c_i, c_i, c_fp]),
     "ynet_seg_onehot_pad": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp]),
     "ynet_resize_nearest": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_fp]),

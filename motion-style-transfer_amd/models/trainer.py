@@ -195,6 +195,16 @@ def radial_report_of(df_metrics, return_radial, fde=None):
                          df_metrics[[f"best_of_{k}_upper_goal" for k in opt["k"]]].to_numpy(), fde)
 
 
+def marginals_report_of(df_metrics, return_marginals, fde=None):
+    """The lines test(return_marginals=...) prints per round (utils.marginals.marginals_report), from evaluate()'s crps_x_goal / crps_y_goal
+    and width<pct>_<axis>_goal / inside<pct>_<axis>_goal columns, beside the round's sampled FDE."""
+    from ..utils.marginals import marginal_levels, marginals_report
+    from ..utils.sharpness import level_name
+    levels = marginal_levels(return_marginals, "test(return_marginals=...)")
+    per_axis = lambda stem: np.stack([df_metrics[[f"{stem}{level_name(q)}_{axis}_goal" for q in levels]].to_numpy() for axis in "xy"], axis=1)
+    return marginals_report(levels, df_metrics[["crps_x_goal", "crps_y_goal"]].to_numpy(), per_axis("inside"), per_axis("width"), fde)
+
+
 class YNetTrainer:
     def __init__(self, params, device=None):
         self.params = params
@@ -320,7 +330,7 @@ class YNetTrainer:
 
     # ------------------------------------------------------------------------------------------
     def test(self, df_test, image_path, return_preds=False, return_samples=False, return_likelihood=False, return_compliance=False,
-             return_radial=False, return_sharpness=False):
+             return_marginals=False, return_radial=False, return_sharpness=False):
         """``return_likelihood`` (not in the reference): evaluate() also scores the goal-map distribution against the ground truth
         (df_metrics columns nll, nll_goal, entropy_goal, hpd_goal) and every round prints its mean NLL and calibration error.
         ``return_compliance`` (not in the reference): evaluate() also reports where in the scene the goals go (df_metrics columns
@@ -332,15 +342,20 @@ class YNetTrainer:
         ``return_radial`` (not in the reference; False, True = {'radii': (4, 8, 16), 'k': (1, 5, 20)}, or such a dict): evaluate() also
         reports the goal error the goal map implies with no draw (df_metrics columns radial_mean_goal, radial_rms_goal, hit<r>_goal,
         best_of_<K>_lower_goal / _upper_goal) and every round prints, for the last step, the expected error of one draw, the bracket
-        around the expected best-of-K error beside the round's sampled FDE, and the mass within each radius."""
+        around the expected best-of-K error beside the round's sampled FDE, and the mass within each radius.
+        ``return_marginals`` (not in the reference; False, True = (0.5, 0.9), or a tuple of levels): evaluate() also scores the goal map
+        per axis (df_metrics columns crps_x_goal, crps_y_goal, crps_goal, pit_x_goal, pit_y_goal, width<pct>_<axis>_goal,
+        inside<pct>_<axis>_goal) and every round prints the mean CRPS beside the round's sampled FDE and, per axis and level, the coverage
+        of the central interval beside its mean width."""
         return self._test(df_test, image_path, return_preds=return_preds, return_samples=return_samples,
                           return_likelihood=return_likelihood, return_compliance=return_compliance, return_sharpness=return_sharpness,
-                          return_radial=return_radial, **self.params)
+                          return_radial=return_radial, return_marginals=return_marginals, **self.params)
 
     def _test(self, df_test, image_path, dataset_name, resize_factor, batch_size, n_round, obs_len, pred_len,
               waypoints, n_goal, n_traj, temperature, rel_threshold, use_TTST, use_CWS, CWS_params,
               use_raw_data=False, return_preds=False, return_samples=False, network=None, swap_semantic=False,
-              return_likelihood=False, return_compliance=False, return_sharpness=False, return_radial=False, **kwargs):
+              return_likelihood=False, return_compliance=False, return_sharpness=False, return_radial=False, return_marginals=False,
+              **kwargs):
         test_images, test_loader, self.homo_mat = self.prepare_data(
             df_test, image_path, dataset_name, "test", obs_len, pred_len, resize_factor, use_raw_data)
         model = self.model.to(self.device)
@@ -355,7 +370,8 @@ class YNetTrainer:
                 "test", n_goal, n_traj, obs_len, batch_size, resize_factor, temperature, use_TTST, use_CWS,
                 rel_threshold, CWS_params, return_preds=return_preds, return_samples=return_samples,
                 network=network, swap_semantic=swap_semantic, dp=self.dp, return_likelihood=return_likelihood,
-                return_compliance=return_compliance, return_sharpness=return_sharpness, return_radial=return_radial)
+                return_compliance=return_compliance, return_sharpness=return_sharpness, return_radial=return_radial,
+                return_marginals=return_marginals)
             list_metrics.append(df_metrics)
             list_trajs.append(trajs_dict)
             print(f"Round {e}: \nTest ADE: {test_ADE} \nTest FDE: {test_FDE}")
@@ -370,6 +386,8 @@ class YNetTrainer:
                 print(sharpness_report_of(df_metrics, test_images, resize_factor))
             if return_radial:
                 print(radial_report_of(df_metrics, return_radial, test_FDE))
+            if return_marginals:
+                print(marginals_report_of(df_metrics, return_marginals, test_FDE))
             self.eval_ADE.append(test_ADE)
             self.eval_FDE.append(test_FDE)
         avg_ade = sum(self.eval_ADE) / len(self.eval_ADE)
@@ -411,9 +429,9 @@ class YNetTrainer:
     def _predict(self, df_obs, image_path, dataset_name, resize_factor, obs_len, waypoints, n_goal, n_traj, temperature,
                  batch_size=None, rel_threshold=0.002, use_TTST=False, use_CWS=False, CWS_params=None, use_raw_data=False,
                  network=None, swap_semantic=False, return_maps=False, bank=None, style_column=None, modes=None, occupancy=None,
-                 **kwargs):
+                 intervals=None, **kwargs):
         import pandas as pd
-        from ..utils.predict import MAX_SAMPLES, predict, predict_modes, predict_styles, predict_with_occupancy
+        from ..utils.predict import MAX_SAMPLES, predict, predict_modes, predict_styles, predict_with_intervals, predict_with_occupancy
         if dataset_name.lower() == "eth":
             raise NotImplementedError("predict: ETH/UCY forecasts are in world coordinates (homographies read from data files): "
                                       "out of the MI355X hot path, as in prepare_data")
@@ -456,6 +474,9 @@ class YNetTrainer:
             elif occupancy is not None:      # the cell edge: predict() plus the scene's occupancy; every scene runs as one chunk
                 res = predict_with_occupancy(model, images[scene_id], observed, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor,
                                              temperature, cell=occupancy, **{**kw, "batch_size": None})
+            elif intervals is not None:      # the levels: predict() plus the per-axis median and central intervals
+                res = predict_with_intervals(model, images[scene_id], observed, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor,
+                                             temperature, levels=intervals, **kw)
             elif bank is None:
                 res = predict(model, images[scene_id], observed, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature, **kw)
             else:
@@ -516,6 +537,18 @@ class YNetTrainer:
         if cell not in (1, 2, 4, 8):      # (before any scene is prepared)
             raise ValueError(f"predict_occupancy: cell = {cell!r}, expected one of (1, 2, 4, 8)")
         return self._predict(df_obs, image_path_or_images, occupancy=int(cell), **self.params)
+
+    def predict_intervals(self, df_obs, image_path_or_images, levels=(0.5, 0.9)):
+        """predict() plus the forecast band per axis, with no draw: where along x and along y every agent will be at step t -- the
+        median and the central interval per level of the goal map's x- and y-marginal (utils.predict.predict_with_intervals).
+        ``df_obs`` and ``image_path_or_images`` as for predict(); ``levels``: 1 .. 8 ascending levels in (0, 1).
+        -> as predict(); every scene's dict carries ``median_xy`` and ``marginal_mean_xy`` [N, pred_len, 2] and ``interval_xy``
+        [N, pred_len, 2, L, 2] (axis; level; lo, hi), in pixels of the resized scene."""
+        from ..utils.marginals import marginal_levels
+        if isinstance(levels, bool) or levels is None:      # (before any scene is prepared)
+            raise ValueError(f"predict_intervals: levels = {levels!r}: a sequence of 1 .. 8 ascending levels in (0, 1) is expected")
+        levels = marginal_levels(levels, "predict_intervals(levels=...)")
+        return self._predict(df_obs, image_path_or_images, intervals=levels, **self.params)
 
     # ------------------------------------------------------------------------------------------
     def forward_test(self, df_test, image_path, set_input, noisy_std_frac):

@@ -2966,6 +2966,51 @@ def check_radial_status(raise_error: bool = True) -> bool:
     return _radial_status.check(raise_error)
 
 
+_marginals_status = _StatusFlag("map_marginals: a ground-truth position is NaN, infinite or more than 16384 pixels outside the map "
+                                "(its crps and pit are NaN)")
+MARGINAL_OUTPUTS = ("col", "row", "crps", "pit")
+MARGINALS_MAX_SIDE = 2048      # YNET_MAP_MARGINALS_MAX_SIDE of include/ynet_hip.h
+
+
+def map_marginals(x: torch.Tensor, gt_xy=None, temperature: float = 1.0, want: Sequence[str] = MARGINAL_OUTPUTS):
+    """The x- and y-marginal of the distribution `sampling` draws from, and their scores against the ground truth (ynet_map_marginals;
+    utils/evaluate.py:128-131, utils/image_utils.py:110-135): per plane of x [B, C, H, W], p = sigmoid(x / T) normalised to sum 1, in
+    one launch.  gt_xy [B, C, 2] (x, y) = (column, row) device coordinates, rounded half-even to a pixel g that may lie OUTSIDE the map
+    (by up to 16384 pixels); None for the marginals alone.
+    -> dict of fp32 device tensors, one per name in ``want``: "col" [B, C, W] = the column sums of p (the x-marginal), "row" [B, C, H] =
+    its row sums, "crps" [B, C, 2] (x, y) = the continuous ranked probability score of each marginal against g, in map pixels (the
+    absolute error for a point forecast; k more for a ground truth k pixels outside the map), "pit" [B, C, 2, 2] (axis; lower, upper) =
+    F(g - 1), F(g) of each marginal's CDF.  utils/marginals.py turns the profiles into quantiles and intervals and the pit into a
+    histogram.  A channel view such as x[:, 1:3] is read in place.  Not differentiable.  Two calls give the same bits.  A NaN logit or
+    Z == 0 makes a plane NaN; a ground truth that is NaN, infinite or farther outside makes its crps and pit NaN and raises at the next
+    check_marginals_status()."""
+    want = _want(want, MARGINAL_OUTPUTS, "map_marginals")
+    t, c, bs = _plane_desc(x.detach() if torch.is_tensor(x) else x, "map_marginals")
+    B, _, H, W = t.shape
+    _check_temperature(temperature, "map_marginals")
+    dev = t.device
+    gt = st = None
+    if gt_xy is None:
+        if "crps" in want or "pit" in want:
+            raise ValueError("map_marginals: crps and pit need the ground truth; without gt_xy ask for want=('col', 'row')")
+    else:
+        gt = _gt_pixels(gt_xy, t, c, "map_marginals")
+        st = _marginals_status.on(dev)
+    tails = {"col": (W,), "row": (H,), "crps": (2,), "pit": (2, 2)}
+    out = {w: torch.empty((B, c) + tails[w], device=dev, dtype=torch.float32) for w in want}
+    ptr = _out_ptrs(out, MARGINAL_OUTPUTS)
+    lib = _lib()
+    L.check(lib.ynet_map_marginals(t.data_ptr(), bs, gt.data_ptr() if gt is not None else None, B, c, H, W, float(temperature),
+                                   ptr["col"], ptr["row"], ptr["crps"], ptr["pit"], st.data_ptr() if st is not None else None, _stream()), lib)
+    return out
+
+
+def check_marginals_status(raise_error: bool = True) -> bool:
+    """Raise if a map_marginals call met a ground truth it could not score (checked at a sync point); the flag is cleared.
+    raise_error=False: report it instead (-> True if one did) -- evaluate() keeps such a plane's NaNs and warns."""
+    return _marginals_status.check(raise_error)
+
+
 MAP_MAX_CLASSES = 8      # YNET_MAP_MAX_CLASSES of include/ynet_hip.h
 
 

@@ -16,7 +16,7 @@ import torch
 from .. import ops
 from . import step_graph
 from .image_utils import SAMPLER, draw_seed, gather_patches, image2world, sampling, swap_pavement_terrain
-from .scores import ComplianceScore, LikelihoodScore, RadialScore, SharpnessScore
+from .scores import ComplianceScore, LikelihoodScore, MarginalScore, RadialScore, SharpnessScore
 
 
 # YNET_SWEEP_STREAMS=0: the K-sample decoder passes of a batch run back to back on one stream
@@ -210,7 +210,8 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
              n_goal, n_traj, obs_len, batch_size, resize_factor=0.25, temperature=1, use_TTST=False, use_CWS=False,
              rel_thresh=0.002, CWS_params=None, return_preds=False, return_samples=False, network=None,
              swap_semantic=False, forced_samples=None, dp=None, max_effective_batch=256, forced_goals=None,
-             forced_ttst_samples=None, return_compliance=False, return_radial=False, return_sharpness=False, return_likelihood=False):
+             forced_ttst_samples=None, return_marginals=False, return_compliance=False, return_radial=False, return_sharpness=False,
+             return_likelihood=False):
     """utils/evaluate.py:37-315.  Extra keyword arguments (tests / data-parallel runs): ``forced_samples`` [K,B,nwp,2]
     per batch replaces every random draw, ``forced_goals`` [n_goal,B,1,2] per batch only the goal draw,
     ``forced_ttst_samples`` [10000,B,1,2] per batch the TTST draw; ``dp`` shards each batch over ranks.
@@ -218,10 +219,11 @@ def evaluate(model, val_loader, val_images, device, dataset_name, homo_mat, inpu
     ``return_likelihood``  nll, entropy and hpd against the ground truth: LikelihoodScore
     ``return_compliance``  the mass on every semantic class of the scene: ComplianceScore
     ``return_sharpness``   the size of the credible regions at given levels: SharpnessScore
-    ``return_radial``      the goal error the distribution implies, hit rates and expected best-of-K: RadialScore"""
+    ``return_radial``      the goal error the distribution implies, hit rates and expected best-of-K: RadialScore
+    ``return_marginals``   the x- and y-marginal: per-axis CRPS, PIT and central intervals at given levels: MarginalScore"""
     # in the order of df_out's columns (a bad flag value raises here, before anything runs)
     scorers = [s for s in (LikelihoodScore(return_likelihood), ComplianceScore(return_compliance), SharpnessScore(return_sharpness),
-                           RadialScore(return_radial)) if s.on]
+                           RadialScore(return_radial), MarginalScore(return_marginals)) if s.on]
     collecting = sorted(scorers, key=lambda s: s.collect_rank)      # the order of their per-batch status checks
     model.eval()
     waypoints = list(waypoints)

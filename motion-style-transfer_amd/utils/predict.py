@@ -18,7 +18,8 @@ suppression (ops.map_modes), each with the probability mass it claims (DESIGN.md
 
 ``predict_with_entropy``, ``predict_with_compliance`` and ``predict_with_regions`` are predict() plus one read-out of the goal map
 each: its entropy, the share of it on every semantic class of the scene (ops.map_class_mass, DESIGN.md
-section 4.13), and its credible regions (ops.map_credible).  ``predict_with_occupancy`` is predict() plus the
+section 4.13), and its credible regions (ops.map_credible).  ``predict_with_intervals`` is predict() plus the median and
+central intervals of the goal map's x- and y-marginal (ops.map_marginals).  ``predict_with_occupancy`` is predict() plus the
 one read-out that is about the scene and not about an agent: the agents' goal maps summed per step, and the expected conflicts between
 them (ops.map_occupancy).
 """
@@ -115,7 +116,7 @@ def _mode_waypoints(model, wp_sigmoid, pred_goal_map, batch, waypoints, n_modes,
 
 def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template, waypoints, n_goal, n_traj, obs_len, resize_factor, temperature,
               use_TTST, use_CWS, rel_thresh, CWS_params, network, swap_semantic, batch_size, max_effective_batch, forced_samples, return_maps,
-              return_entropy, modes=None, return_compliance=False, occupancy=None, regions=None):
+              return_entropy, modes=None, return_compliance=False, occupancy=None, intervals=None, regions=None):
     """The one body of predict(), predict_with_entropy(), predict_styles() and predict_modes(), on arguments that went through _validated.
     modes              None, or (n_modes, radius): the way-points are not drawn but read off the goal map (_mode_waypoints; then
                        n_goal = n_modes, n_traj = 1, and the results gain ``mode_mass`` and ``mode_logit``)
@@ -123,6 +124,9 @@ def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template
                        utils.compliance.scene_labels(scene_image), the classes of the scene as given (before ``swap_semantic``)
     regions            None, or the credible levels (ops.credible_levels): the results gain ``region_area`` (int32), ``region_threshold``
                        and ``region_mass`` [N, pred_len, L]: one ops.map_credible launch per chunk
+    intervals          None, or the levels of the central intervals (utils.marginals.marginal_levels): the results gain ``median_xy`` and
+                       ``marginal_mean_xy`` [N, pred_len, 2] and ``interval_xy`` [N, pred_len, 2, L, 2] (axis; level; lo, hi) in pixels of
+                       the resized map: one ops.map_marginals launch per chunk, without ground truth
     occupancy          None, or the cell edge (1, 2, 4, 8): the results gain ``occupancy`` and ``occupancy_any`` [pred_len, Hc, Wc],
                        ``conflict`` [pred_len] and ``risk`` [N, pred_len] from one ops.map_occupancy call; the scene must run as ONE
                        chunk (the pairs across two chunks would be lost), anything else is refused before the model is touched
@@ -146,7 +150,8 @@ def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template
            + (["entropy"] if return_entropy else []) + (["mode_mass", "mode_logit"] if modes is not None else [])
            + (["goal_class_mass"] if return_compliance else [])
            + (["region_area", "region_threshold", "region_mass"] if regions is not None else [])
-           + (["occupancy", "occupancy_any", "conflict", "risk"] if occupancy is not None else [])}
+           + (["occupancy", "occupancy_any", "conflict", "risk"] if occupancy is not None else [])
+           + (["median_xy", "interval_xy", "marginal_mean_xy"] if intervals is not None else [])}
     try:
         with torch.no_grad():
             refresh()
@@ -203,6 +208,13 @@ def _forecast(name, model, refresh, chunk_plan, scene_image, obs, input_template
                 if regions is not None:
                     for k, v in ops.map_credible(pred_goal_map, regions, temperature).items():
                         out["region_" + k].append(v)
+                if intervals is not None:
+                    from .marginals import central_intervals, profile_mean, quantiles
+                    marg = ops.map_marginals(pred_goal_map, None, temperature, want=("col", "row"))
+                    axes = (marg["col"], marg["row"])      # (x, y): the index along an axis is the pixel coordinate, as the way-points'
+                    out["median_xy"].append(torch.stack([quantiles(p, (0.5,))[..., 0] for p in axes], dim=-1).float())
+                    out["interval_xy"].append(torch.stack([central_intervals(p, intervals) for p in axes], dim=2).float())
+                    out["marginal_mean_xy"].append(torch.stack([profile_mean(p) for p in axes], dim=-1).float())
                 if occupancy is not None:      # (one group: the chunk is the scene)
                     occ = ops.map_occupancy(pred_goal_map, None, occupancy, temperature)
                     out["occupancy"].append(occ["occupancy"][0])
@@ -300,6 +312,29 @@ def predict_with_regions(*args, levels=(0.5, 0.9), **kwargs):
     bound = _PREDICT_SIGNATURE.bind(*args, **kwargs)
     bound.apply_defaults()
     return _predict(False, **bound.arguments, regions=regions)
+
+
+def predict_with_intervals(*args, levels=(0.5, 0.9), **kwargs):
+    """predict() with the same arguments, and three more results (device tensors, float32): the forecast band per axis, as a pure function
+    of (weights, scene, observed steps) -- per future step, from the x- and the y-marginal of the goal-map distribution (sigmoid(pred_goal_map
+    / T) normalised per plane, what `sampling` draws from; its column and row sums):
+      ``median_xy``         [N, pred_len, 2]         the median of each marginal
+      ``interval_xy``       [N, pred_len, 2, L, 2]   (axis; level; lo, hi) the central interval per level q of ``levels`` (keyword only; 1 .. 8
+                                                     strictly ascending values inside (0, 1)): its (1 - q) / 2 and (1 + q) / 2 quantiles, ends included
+      ``marginal_mean_xy``  [N, pred_len, 2]         the mean of each marginal
+    in pixels of the resized scene, the coordinates of ``waypoints`` (a quantile is the smallest pixel index whose CDF reaches it: utils.marginals).
+    One ops.map_marginals launch per chunk without ground truth; the intervals are the ones
+    evaluate(return_marginals=levels) reports as ``interval_steps``.  No draw; every other result is predict()'s, bit for bit.  A plane
+    that holds a NaN has median and interval -1 and a NaN mean.
+    (A function of its own and not a keyword of predict(), as predict_with_entropy(): predict()'s parameter list is pinned by
+    tests/test_predict_host.py, and predict_styles mirrors it.)"""
+    from .marginals import marginal_levels
+    if isinstance(levels, bool) or levels is None:
+        raise ValueError(f"predict_with_intervals: levels = {levels!r}: a sequence of 1 .. 8 ascending levels in (0, 1) is expected")
+    intervals = marginal_levels(levels, "predict_with_intervals")
+    bound = _PREDICT_SIGNATURE.bind(*args, **kwargs)
+    bound.apply_defaults()
+    return _predict(False, **bound.arguments, intervals=intervals)
 
 
 def predict_with_occupancy(*args, cell=4, **kwargs):

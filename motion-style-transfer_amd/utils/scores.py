@@ -12,6 +12,7 @@ import torch
 
 from .. import ops
 from .compliance import MAX_CLASSES, class_rates, point_classes, scene_labels
+from .marginals import central_intervals, inside_intervals, marginal_levels
 from .radial import radial_options, radial_summary
 from .sharpness import inside_regions, level_name, sharpness_levels
 
@@ -226,3 +227,60 @@ class RadialScore(Score):
         for j, k in enumerate(self.ks):
             df_out[f"best_of_{k}_lower_goal"] = a["best_of_k_lower"][:, -1, j]
             df_out[f"best_of_{k}_upper_goal"] = a["best_of_k_upper"][:, -1, j]
+
+
+class MarginalScore(Score):
+    """``return_marginals`` (False, True = (0.5, 0.9), or a tuple of 1 .. 8 ascending levels in (0, 1)): the distribution per axis
+    (ops.map_marginals, utils/marginals.py, DESIGN.md section 4.17), from the x- and the y-marginal of every step's plane (resized pixels;
+    a ground truth outside the map is scored too).  df_out gains, for the last step, ``crps_x_goal``, ``crps_y_goal`` and ``crps_goal``
+    (their sum) -- the continuous ranked probability score, a proper score in the units of the sdd FDE, resized pixels / resize_factor --
+    ``pit_x_goal`` and ``pit_y_goal`` (the mid-point of the probability integral transform's two ends), and per level
+    ``width<pct>_x_goal`` / ``width<pct>_y_goal`` (hi - lo of the central interval, in the units of the CRPS columns) and
+    ``inside<pct>_x_goal`` / ``inside<pct>_y_goal`` (1.0 / 0.0: the rounded ground truth lies inside it; NaN where it cannot be scored);
+    with ``return_preds`` trajs_dict gains ``crps_steps`` [N, pred_len, 2], ``pit_steps`` [N, pred_len, 2, 2] and ``interval_steps``
+    [N, pred_len, 2, L, 2] (axis; level; lo, hi pixel indices of the resized map).  Only these reduced quantities are kept per batch,
+    never the profiles.  A plane that cannot be scored (a NaN logit; a ground truth that is NaN or more than 16384 pixels outside the
+    map) is NaN (one warning per call for the latter)."""
+    keys = ("crps", "pit", "interval", "inside", "width")
+    status = "marginals"
+    warning = ("evaluate(return_marginals=...): a ground-truth position is NaN or more than 16384 pixels outside the "
+               "map; its crps, pit and inside columns are NaN (ADE / FDE are unaffected)")
+
+    def __init__(self, return_marginals):
+        self.levels = marginal_levels(return_marginals)
+        super().__init__(self.levels is not None)
+
+    def score(self, pred_goal_map, gt_future, temperature, H, W, resize_factor, scene_id):
+        m = ops.map_marginals(pred_goal_map, gt_future, temperature)
+        interval = torch.stack([central_intervals(m["col"], self.levels), central_intervals(m["row"], self.levels)], dim=2)
+        inside = inside_intervals(interval, gt_future.to(interval.device))      # [n, pred_len, 2 (x, y), L]
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=inside.device)
+        inside = torch.where(~torch.isnan(m["crps"])[..., None], inside, nan)      # (a ground truth the launch could not score)
+        width = torch.where(interval[..., 0] >= 0, (interval[..., 1] - interval[..., 0]).double() / resize_factor, nan)      # the units of evaluate()'s ADE / FDE
+        return {"crps": m["crps"].double() / resize_factor, "pit": m["pit"], "interval": interval, "inside": inside, "width": width}
+
+    def empty(self, steps, device, scene_id):
+        L = len(self.levels)
+        return {"crps": torch.zeros((0, steps, 2), device=device, dtype=torch.float64), "pit": torch.zeros((0, steps, 2, 2), device=device),
+                "interval": torch.zeros((0, steps, 2, L, 2), device=device, dtype=torch.int64),
+                "inside": torch.zeros((0, steps, 2, L), device=device, dtype=torch.float64),
+                "width": torch.zeros((0, steps, 2, L), device=device, dtype=torch.float64)}
+
+    def columns(self, df_out):
+        a = self.arrays()
+        df_out["crps_x_goal"] = a["crps"][:, -1, 0]
+        df_out["crps_y_goal"] = a["crps"][:, -1, 1]
+        df_out["crps_goal"] = a["crps"][:, -1, 0] + a["crps"][:, -1, 1]
+        pit = a["pit"].astype(np.float64)
+        df_out["pit_x_goal"] = 0.5 * (pit[:, -1, 0, 0] + pit[:, -1, 0, 1])
+        df_out["pit_y_goal"] = 0.5 * (pit[:, -1, 1, 0] + pit[:, -1, 1, 1])
+        for l, q in enumerate(self.levels):
+            for j, axis in enumerate("xy"):
+                df_out[f"width{level_name(q)}_{axis}_goal"] = a["width"][:, -1, j, l]
+                df_out[f"inside{level_name(q)}_{axis}_goal"] = a["inside"][:, -1, j, l]
+
+    def steps(self, trajs_dict):
+        a = self.arrays()
+        trajs_dict["crps_steps"] = a["crps"]
+        trajs_dict["pit_steps"] = a["pit"]
+        trajs_dict["interval_steps"] = a["interval"]

@@ -375,6 +375,22 @@ int main() {
         EXPECT_REJECT(ynet_map_radial(cfp, 31, cfp, 2, 2, 4, 4, 1.f, 5, fp, fp, fp, fp, &status, nullptr));                           // batch stride below the image
         EXPECT_REJECT(ynet_map_radial(cfp, 4, cfp, 1ll << 29, 4, 1, 1, 1.f, 5, fp, fp, fp, fp, &status, nullptr));                    // 2^31 planes
     }
+    {   // marginals: the refusals (the ground truth is device data: the host never reads it)
+        EXPECT_REJECT(ynet_map_marginals(nullptr, 16, cfp, 1, 1, 4, 4, 1.f, fp, fp, fp, fp, &status, nullptr));                       // no map
+        EXPECT_REJECT(ynet_map_marginals(cfp, 16, cfp, 1, 1, 4, 4, 1.f, nullptr, nullptr, nullptr, nullptr, &status, nullptr));       // no output
+        EXPECT_REJECT(ynet_map_marginals(cfp, 16, nullptr, 1, 1, 4, 4, 1.f, fp, fp, fp, nullptr, &status, nullptr));                  // crps without a ground truth
+        EXPECT_REJECT(ynet_map_marginals(cfp, 16, nullptr, 1, 1, 4, 4, 1.f, fp, fp, nullptr, fp, &status, nullptr));                  // pit without one
+        EXPECT_REJECT(ynet_map_marginals(cfp, 16, cfp, 1, 1, 4, 4, 1.f, fp, fp, fp, fp, nullptr, nullptr));                           // ... without a status flag
+        EXPECT_REJECT(ynet_map_marginals(cfp, 16, cfp, 1, 1, 4, 4, 0.f, fp, fp, fp, fp, &status, nullptr));                           // temperature 0
+        EXPECT_REJECT(ynet_map_marginals(cfp, 16, cfp, 1, 1, 4, 4, 0.f / 0.f, fp, fp, fp, fp, &status, nullptr));                     // not finite
+        EXPECT_REJECT(ynet_map_marginals(cfp, 16, cfp, 1, 1, 4, 4, 1e-39f, fp, fp, fp, fp, &status, nullptr));                        // a denormal: 1 / T overflows
+        EXPECT_REJECT(ynet_map_marginals(cfp, 16, cfp, 0, 1, 4, 4, 1.f, fp, fp, fp, fp, &status, nullptr));                           // B, C, H, W < 1
+        EXPECT_REJECT(ynet_map_marginals(cfp, 16, cfp, 1, 1, 4, 0, 1.f, fp, fp, fp, fp, &status, nullptr));
+        EXPECT_REJECT(ynet_map_marginals(cfp, 1ll << 20, cfp, 1, 1, YNET_MAP_MARGINALS_MAX_SIDE + 1, 1, 1.f, fp, fp, fp, fp, &status, nullptr));   // a side above 2048
+        EXPECT_REJECT(ynet_map_marginals(cfp, 1ll << 20, nullptr, 1, 1, 1, YNET_MAP_MARGINALS_MAX_SIDE + 1, 1.f, fp, fp, nullptr, nullptr, nullptr, nullptr));
+        EXPECT_REJECT(ynet_map_marginals(cfp, 31, cfp, 2, 2, 4, 4, 1.f, fp, fp, fp, fp, &status, nullptr));                           // batch stride below the image
+        EXPECT_REJECT(ynet_map_marginals(cfp, 4, cfp, 1ll << 29, 4, 1, 1, 1.f, fp, fp, fp, fp, &status, nullptr));                    // 2^31 planes
+    }
     {   // the sweep reads its temperatures on the host: exactly n_temps of them (a heap array of that length, so a read past it is seen)
         float* t32 = new float[YNET_SWEEP_MAX_TEMPS];
         float* t3 = new float[3];
