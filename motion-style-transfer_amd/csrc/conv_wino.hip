@@ -363,6 +363,32 @@ __device__ __forceinline__ void wino_kstep(f32x4 (&acc)[16][NCB], const f32x2 (&
     }
 }
 
+// Where a unit lies -- image, first output row, first output column --, decoded ONCE per unit, when the wave takes the unit from the
+// workgroup's counter: the three divisions by run-time divisors stay out of the chunk loop, and the epilogue takes the same decode
+// (DESIGN.md section 4.1).  tile_h: output rows of a tile, unit_h: of a unit; u8: the unit's index in its tile.
+// The slice form, the cat form and both up-convolution forms use it.  conv_wino_kernel below keeps its decode per chunk: with 8 channels
+// per chunk it pays 4 decodes per unit, not 16, measured no gain from the context (+-0.5 % per launch), and its predictor form EM 8
+// spilled nine more scalar registers with it.
+struct WinoPlace {
+    int b, y0, x0;
+};
+__device__ __forceinline__ WinoPlace wino_place(int t, int u8, int tiles_x, int tiles_y, int tile_h, int unit_h) {
+    const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y;
+    return WinoPlace{t / (tiles_x * tiles_y), ty * tile_h + unit_h * u8, tx * WN_TW};
+}
+
+// The DMA cursor of the up-convolution forms (one source): the input descriptor of the image being fetched and the scalar offset of the next chunk.
+// A wave fetches its chunks strictly in order -- those of a unit, then those of the next --, so one cursor serves both: it is pointed at
+// a unit once (enter: one 64-bit multiply, one descriptor) and then only stepped (so += the chunk's planes).
+struct WinoFeed1 {
+    __amdgpu_buffer_rsrc_t rx;
+    unsigned so;
+    __device__ __forceinline__ void enter(const unsigned char* img, unsigned bytes, unsigned base) {
+        rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(img), 0, bytes, 0x00020000);
+        so = base;
+    }
+};
+
 // NCB: 16-channel output blocks (cout = 16 NCB), NCH: chunks of 8 input channels (cin = 8 NCH; even: chunk c lives in slot c & 1 of the
 // wave's ring, and the chunk two ahead -- of this pair or the next -- takes the slot just read)
 template <int NCB, int NCH, int EM, int NW>
@@ -686,6 +712,41 @@ struct WinoCatArgs {
     unsigned* wbits;           // EPI 4 / 5 (= 0 / 2 + the Winograd-native 1-bit mask of the output written, see wino_epilogue)
 };
 
+// The DMA cursor of the multi-source kernels (this one and the slice form): (source s, real channels left in it) of the next chunk to
+// fetch, that source's descriptor for the image of the unit being fetched, and the chunk's scalar offset.  A wave fetches its chunks
+// strictly in order -- those of a unit, then those of the next --, so the chunk -> source mapping is a running pair: per chunk the cursor
+// only steps (so += 4 planes, left -= 4).  The kernel arguments of a source are read, its image base multiplied out (a batch stride of 0,
+// the shared scene, needs no special case) and its descriptor built where the cursor ENTERS the source: once per source and unit, not
+// once per chunk.  (Every source has at least one channel: ynet_conv2d_winograd_cat / ynet_conv2d_winograd16 require it.)
+struct WinoSrcFeed {
+    __amdgpu_buffer_rsrc_t rx;
+    unsigned so;          // base + (the chunk's first channel in its source) * plane bytes
+    unsigned base;        // of the unit: (y0 * W + x0) * 4
+    int left, s, b;       // the chunk has min(4, left) real channels; left <= 0: the next chunk is the first of source s + 1
+
+    __device__ __forceinline__ void start(int b_, unsigned base_) {      // a unit's first chunk is the next one
+        b = b_;
+        base = base_;
+        s = -1;
+        left = 0;
+    }
+    // in front of a chunk's DMA; plane: bytes of a plane, lead: bytes the descriptors start in front of the image
+    template <typename Args>
+    __device__ __forceinline__ void source(const Args& a, unsigned plane, unsigned lead) {
+        if (left <= 0) {
+            ++s;
+            left = a.x_c[s];
+            rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(a.x[s] + (long long)b * a.x_bs[s]) - lead), 0,
+                                                   (unsigned)left * plane + lead, 0x00020000);
+            so = base;
+        }
+    }
+    __device__ __forceinline__ void step(unsigned plane) {      // behind it
+        so += 4u * plane;
+        left -= 4;
+    }
+};
+
 template <int NCB, int EPI_>
 __global__ __launch_bounds__(WN_THREADS, 1) void conv_wino_cat_kernel(const WinoCatArgs a) {
     constexpr int EPI = EPI_ == 4 ? 0 : (EPI_ == 5 ? 2 : (EPI_ == 6 ? 3 : EPI_));
@@ -753,42 +814,47 @@ __global__ __launch_bounds__(WN_THREADS, 1) void conv_wino_cat_kernel(const Wino
         return (int)__builtin_amdgcn_readfirstlane(u);
     };
 
-    // chunk c of row pair `unit` -> slot `slot` (the wave's running chunk count & 1): three DMA instructions, always
-    auto dma_chunk = [&](int unit, int c, int slot) {
-        const int t = tile_first + (unit >> 3) * gstride;
-        const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
-        const int y0 = ty * WN_TH + 2 * (unit & 7), x0 = tx * WN_TW;
+    // the unit contexts: `cu` the place of the unit being computed (the epilogue's), `nx` the unit taken from the counter after it, `feed` the DMA cursor --
+    // in `cur` until its last chunk is issued, then in `nxt` (whose first two chunks are fetched under cur's last two k-steps)
+    auto place = [&](int unit) { return wino_place(tile_first + (unit >> 3) * gstride, unit & 7, tiles_x, tiles_y, WN_TH, 2); };
+    WinoSrcFeed feed;
+    const unsigned plane = (unsigned)(HW * 4);
+    unsigned fv[3];                         // the lane's offsets for the unit being fetched: rel[], or beyond the descriptor on an edge the unit touches
+    auto feed_unit = [&](WinoPlace p) {
+        const int y0 = p.y0, x0 = p.x0;
         const unsigned em = (y0 == 0 ? 1u : 0u) | (y0 + 2 == H ? 2u : 0u) | (x0 == 0 ? 4u : 0u) | (x0 + WN_TW == W ? 8u : 0u);
-        // the chunk's source and its first channel there
-        int s = 0, ch = c * 4;
-        while (s + 1 < a.nsrc && ch >= ((a.x_c[s] + 3) & ~3)) {
-            ch -= (a.x_c[s] + 3) & ~3;
-            ++s;
-        }
-        const unsigned nvalid = (unsigned)min(4, a.x_c[s] - ch);
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(a.x[s] + (long long)b * a.x_bs[s]) - lead), 0,
-            (unsigned)(a.x_c[s] * HW * 4) + lead, 0x00020000);
-        const unsigned so = (unsigned)((ch * HW + y0 * W + x0) * 4);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) fv[j] = (edge[j] & em) ? 0x80000000u : rel[j];
+        feed.start(p.b, (unsigned)((y0 * W + x0) * 4));
+    };
+    // the cursor's chunk -> slot `slot` (the wave's running chunk count & 1): three DMA instructions, always
+    auto dma_next = [&](int slot) {
         const unsigned sb = ring0 + (unsigned)(slot * WC_SLOT_BYTES) + 4u;
-        if (em == 0 && nvalid == 4) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(uintptr_t)sb, 16, rel[0], so, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(uintptr_t)(sb + 1024u), 16, rel[1], so, 0, 0);
-            if (lane < 32) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(uintptr_t)(sb + 2048u), 16, rel[2], so, 0, 0);
+        feed.source(a, plane, lead);
+        const unsigned so = feed.so;
+        if (feed.left >= 4) {
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(feed.rx, (lds_ptr_t)(uintptr_t)sb, 16, fv[0], so, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(feed.rx, (lds_ptr_t)(uintptr_t)(sb + 1024u), 16, fv[1], so, 0, 0);
+            if (lane < 32) __builtin_amdgcn_raw_ptr_buffer_load_lds(feed.rx, (lds_ptr_t)(uintptr_t)(sb + 2048u), 16, fv[2], so, 0, 0);
         } else {
-            const unsigned v0 = ((edge[0] & em) || planeof[0] >= nvalid) ? 0x80000000u : rel[0];
-            const unsigned v1 = ((edge[1] & em) || planeof[1] >= nvalid) ? 0x80000000u : rel[1];
-            const unsigned v2 = ((edge[2] & em) || planeof[2] >= nvalid) ? 0x80000000u : rel[2];
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(uintptr_t)sb, 16, v0, so, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(uintptr_t)(sb + 1024u), 16, v1, so, 0, 0);
-            if (lane < 32) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(uintptr_t)(sb + 2048u), 16, v2, so, 0, 0);
+            const unsigned nvalid = (unsigned)feed.left;
+            const unsigned v0 = planeof[0] >= nvalid ? 0x80000000u : fv[0];
+            const unsigned v1 = planeof[1] >= nvalid ? 0x80000000u : fv[1];
+            const unsigned v2 = planeof[2] >= nvalid ? 0x80000000u : fv[2];
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(feed.rx, (lds_ptr_t)(uintptr_t)sb, 16, v0, so, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(feed.rx, (lds_ptr_t)(uintptr_t)(sb + 1024u), 16, v1, so, 0, 0);
+            if (lane < 32) __builtin_amdgcn_raw_ptr_buffer_load_lds(feed.rx, (lds_ptr_t)(uintptr_t)(sb + 2048u), 16, v2, so, 0, 0);
         }
+        feed.step(plane);
     };
 
     int cur = wave, nxt = next_unit();
     int g = 0;                              // the wave's running chunk count: chunk g lives in slot g & 1
-    dma_chunk(cur, 0, 0);
-    dma_chunk(cur, 1, 1);
+    WinoPlace cu = place(cur), nx = cu;
+    feed_unit(cu);
+    dma_next(0);
+    dma_next(1);
+    if (nxt < total_units) nx = place(nxt);
 
     f32x4 acc[16][NCB];
     const unsigned char* ringp = reinterpret_cast<const unsigned char*>(smem) + wbytes + wave * WC_RING_BYTES;
@@ -807,29 +873,34 @@ __global__ __launch_bounds__(WN_THREADS, 1) void conv_wino_cat_kernel(const Wino
             }
             // the slot is read out (this wave's own reads): it takes the chunk two ahead
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (c + 2 < nchunks) dma_chunk(cur, c + 2, slot);
-            else if (nxt < total_units) dma_chunk(nxt, c + 2 - nchunks, slot);
+            if (c + 2 < nchunks || nxt < total_units) {
+                if (c + 2 == nchunks) feed_unit(nx);      // (the hand-over: cur's last chunk is on its way)
+                dma_next(slot);
+            }
             wino_kstep<NCB, decltype(first)::value>(acc, dl, dh, smem + c * WQ, lane);
             ++g;
         };
         step(0, std::true_type{});          // (the pair's first k-step accumulates onto 0: peeled, no run-time branch around the MFMAs)
         for (int c = 1; c < nchunks; ++c) step(c, std::false_type{});
         {
-            const int t = tile_first + (cur >> 3) * gstride;
-            const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
-            const unsigned so_t = (unsigned)(((ty * WN_TH + 2 * (cur & 7)) * W + tx * WN_TW) * 4);
+            const int b = cu.b, y0 = cu.y0, x0 = cu.x0;
+            const unsigned so_t = (unsigned)((y0 * W + x0) * 4);
             const int ab = a.addend_bmod > 0 ? b % a.addend_bmod : b;
-            const unsigned sa_t = EPI == 3 ? (unsigned)(((ty * (WN_TH / 2) + (cur & 7)) * (W >> 1) + tx * (WN_TW / 2)) * 4) : so_t;
+            const unsigned sa_t = EPI == 3 ? (unsigned)(((y0 >> 1) * (W >> 1) + (x0 >> 1)) * 4) : so_t;
             const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y + (long long)b * a.y_bs, 0, y_img, 0x00020000);
             const __amdgpu_buffer_rsrc_t ra =
                 EPI == 3 ? __builtin_amdgcn_make_buffer_rsrc(a.pool + (long long)b * a.pool_bs, 0, y_img >> 2, 0x00020000)
                          : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ADD ? a.addend + (long long)ab * a.addend_bs : a.y), 0, y_img, 0x00020000);
-            unsigned* wb = BITS == 1 ? a.wbits + (((long long)b * (H >> 1) + (ty * (WN_TH / 2) + (cur & 7))) * tiles_x + tx) * 64 + lane : nullptr;
+            unsigned* wb = BITS == 1 ? a.wbits + (((long long)b * (H >> 1) + (y0 >> 1)) * tiles_x + x0 / WN_TW) * 64 + lane : nullptr;
             unsigned char* pc = BITS == 3 ? a.pcode + ((long long)b * (16 * NCB) * (HW >> 2) + ((stp + sa_t) >> 2)) : nullptr;      // (the pooled copy's element index)
             wino_epilogue<NCB, EPI, BITS>(acc, bias2, floor_v, ry, ra, st0, st1, so_t, sa_t, HW, stp, wb, pc);
         }
         cur = nxt;
-        if (cur < total_units) nxt = next_unit();
+        cu = nx;
+        if (cur < total_units) {
+            nxt = next_unit();
+            if (nxt < total_units) nx = place(nxt);
+        }
     }
 }
 
@@ -962,36 +1033,44 @@ __global__ __launch_bounds__(WN_THREADS, 1) void conv_wino16_kernel(const Wino16
         return (int)__builtin_amdgcn_readfirstlane(u);
     };
 
-    // chunk c of unit `unit` -> slot: four DMA instructions (one per input channel of the chunk), always
-    auto dma_chunk = [&](int unit, int c, int slot) {
-        const int t = tile_first + (unit >> 3) * gstride;
-        const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
-        const int y0 = ty * W6_TH + 4 * (unit & 7), x0 = tx * WN_TW;
+    // the unit contexts, as in conv_wino_cat_kernel: `cu` the place of the unit being computed, `nx` the unit taken after it, `feed` the DMA cursor
+    auto place = [&](int unit) { return wino_place(tile_first + (unit >> 3) * gstride, unit & 7, tiles_x, tiles_y, W6_TH, 4); };
+    WinoSrcFeed feed;
+    const unsigned plane = (unsigned)(HW * 4);
+    unsigned fv;                            // the lane's offset for the unit being fetched: rel, or beyond the descriptor on an edge the unit touches
+    auto feed_unit = [&](WinoPlace p) {
+        const int y0 = p.y0, x0 = p.x0;
         const unsigned em = (y0 == 0 ? 1u : 0u) | (y0 + 4 == H ? 2u : 0u) | (x0 == 0 ? 4u : 0u) | (x0 + WN_TW == W ? 8u : 0u);
-        int s = 0, ch = c * 4;
-        while (s + 1 < a.nsrc && ch >= ((a.x_c[s] + 3) & ~3)) {
-            ch -= (a.x_c[s] + 3) & ~3;
-            ++s;
-        }
-        const int nvalid = min(4, a.x_c[s] - ch);
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(a.x[s] + (long long)b * a.x_bs[s]) - lead), 0,
-            (unsigned)(a.x_c[s] * HW * 4) + lead, 0x00020000);
-        const unsigned so = (unsigned)((ch * HW + y0 * W + x0) * 4);
+        fv = (edge & em) ? 0x80000000u : rel;
+        feed.start(p.b, (unsigned)((y0 * W + x0) * 4));
+    };
+    // the cursor's chunk -> slot: four DMA instructions (one per input channel of the chunk), always
+    auto dma_next = [&](int slot) {
         const unsigned sb = ring0 + (unsigned)(slot * W6_SLOT_BYTES) + 4u;
-        const unsigned v = (edge & em) ? 0x80000000u : rel;
+        feed.source(a, plane, lead);
+        const unsigned so = feed.so;
         if (lane < 60) {
+            if (feed.left >= 4) {
 #pragma unroll
-            for (int p = 0; p < 4; ++p)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(uintptr_t)(sb + (unsigned)(p * W6_PLANE_BYTES)), 16, p < nvalid ? v : 0x80000000u,
-                                                         so + (unsigned)(p * HW * 4), 0, 0);
+                for (int p = 0; p < 4; ++p)
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(feed.rx, (lds_ptr_t)(uintptr_t)(sb + (unsigned)(p * W6_PLANE_BYTES)), 16, fv, so + (unsigned)p * plane, 0, 0);
+            } else {
+#pragma unroll
+                for (int p = 0; p < 4; ++p)
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(feed.rx, (lds_ptr_t)(uintptr_t)(sb + (unsigned)(p * W6_PLANE_BYTES)), 16, p < feed.left ? fv : 0x80000000u,
+                                                             so + (unsigned)p * plane, 0, 0);
+            }
         }
+        feed.step(plane);
     };
 
     int cur = wave, nxt = next_unit();
     int g = 0;                              // the wave's running chunk count: chunk g lives in slot g & 1
-    dma_chunk(cur, 0, 0);
-    dma_chunk(cur, 1, 1);
+    WinoPlace cu = place(cur), nx = cu;
+    feed_unit(cu);
+    dma_next(0);
+    dma_next(1);
+    if (nxt < total_units) nx = place(nxt);
 
     f32x4 acc[2][16][1];
     const unsigned char* ringp = reinterpret_cast<const unsigned char*>(smem) + wbytes + wave * W6_RING_BYTES;
@@ -1008,17 +1087,17 @@ __global__ __launch_bounds__(WN_THREADS, 1) void conv_wino16_kernel(const Wino16
                 dh[r] = *reinterpret_cast<const f32x2*>(ip + r * WN_ROWF + 2);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (c + 2 < nchunks) dma_chunk(cur, c + 2, slot);
-            else if (nxt < total_units) dma_chunk(nxt, c + 2 - nchunks, slot);
+            if (c + 2 < nchunks || nxt < total_units) {
+                if (c + 2 == nchunks) feed_unit(nx);      // (the hand-over: cur's last chunk is on its way)
+                dma_next(slot);
+            }
             wino16_kstep<decltype(first)::value>(acc, dl, dh, smem + c * WQ, lane);
             ++g;
         };
         step(0, std::true_type{});
         for (int c = 1; c < nchunks; ++c) step(c, std::false_type{});
         {
-            const int t = tile_first + (cur >> 3) * gstride;
-            const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
-            const int y0 = ty * W6_TH + 4 * (cur & 7), x0 = tx * WN_TW;
+            const int b = cu.b, y0 = cu.y0, x0 = cu.x0;
             const int ab = (EPI == 2 && a.aux_bmod > 0) ? b % a.aux_bmod : b;
             const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y + (long long)b * a.y_bs + (long long)slice * 16 * HW, 0, y_img, 0x00020000);
             const __amdgpu_buffer_rsrc_t rm =
@@ -1033,7 +1112,11 @@ __global__ __launch_bounds__(WN_THREADS, 1) void conv_wino16_kernel(const Wino16
             }
         }
         cur = nxt;
-        if (cur < total_units) nxt = next_unit();
+        cu = nx;
+        if (cur < total_units) {
+            nxt = next_unit();
+            if (nxt < total_units) nx = place(nxt);
+        }
     }
 }
 
@@ -1120,16 +1203,15 @@ __global__ __launch_bounds__(WN_THREADS, 1) void conv_wino_up_kernel(const WinoU
         return (int)__builtin_amdgcn_readfirstlane(u);
     };
 
-    auto dma_chunk = [&](int unit, int c) {       // the three low-resolution rows under row pair `unit`, chunk c -> slot c & 1
-        const int t = tile_first + (unit >> 3) * gstride, slot = c & 1;
-        const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
-        const int i = (ty * WN_TH >> 1) + (unit & 7), j0 = tx * (WN_TW / 2);
+    // the unit contexts: `cu` the place of the row pair being computed, `nx` the place and the image of the one taken after it, `feed` the DMA cursor (in `cur`
+    // until its last chunk is issued, then in `nxt`)
+    auto place = [&](int unit) { return wino_place(tile_first + (unit >> 3) * gstride, unit & 7, tiles_x, tiles_y, WN_TH, 2); };
+    auto image = [&](int b) { return reinterpret_cast<const unsigned char*>(a.x + (long long)b * a.x_bs) - lead; };
+    WinoFeed1 feed;
+    unsigned fv[3];                         // the lane's offsets for the row pair being fetched
+    auto feed_unit = [&](WinoPlace p, const unsigned char* img) {
+        const int i = p.y0 >> 1, j0 = p.x0 >> 1;      // the row pair's low-resolution row and first column
         const unsigned em = (i == 0 ? 1u : 0u) | (i + 1 == Hl ? 2u : 0u) | (j0 == 0 ? 4u : 0u) | (j0 + WN_TW / 2 == Wl ? 8u : 0u);
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(a.x + (long long)b * a.x_bs) - lead), 0, x_img, 0x00020000);
-        const unsigned so = (unsigned)((c * 8 * HWl + i * Wl + j0) * 4);
-        const unsigned sb = ring0 + (unsigned)(slot * WU_SLOT_BYTES);
-        unsigned v[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             // the row above the image is row 0, the row below it the last row (bilinear clamp); units left / right of the image: zero
@@ -1137,24 +1219,34 @@ __global__ __launch_bounds__(WN_THREADS, 1) void conv_wino_up_kernel(const WinoU
             unsigned o = rel[j];
             if (edge[j] & em & 1u) o += (unsigned)(Wl * 4);
             if (edge[j] & em & 2u) o -= (unsigned)(Wl * 4);
-            v[j] = (edge[j] & em & 12u) ? 0x80000000u : o;
+            fv[j] = (edge[j] & em & 12u) ? 0x80000000u : o;
         }
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(uintptr_t)sb, 16, v[0], so, 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(uintptr_t)(sb + 1024u), 16, v[1], so, 0, 0);
-        if (lane < 16) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(uintptr_t)(sb + 2048u), 16, v[2], so, 0, 0);
+        feed.enter(img, x_img, (unsigned)((i * Wl + j0) * 4));
+    };
+    auto dma_next = [&](int slot) {       // the three low-resolution rows under the cursor's row pair, its next chunk -> slot (the chunk's index & 1)
+        const unsigned sb = ring0 + (unsigned)(slot * WU_SLOT_BYTES);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(feed.rx, (lds_ptr_t)(uintptr_t)sb, 16, fv[0], feed.so, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(feed.rx, (lds_ptr_t)(uintptr_t)(sb + 1024u), 16, fv[1], feed.so, 0, 0);
+        if (lane < 16) __builtin_amdgcn_raw_ptr_buffer_load_lds(feed.rx, (lds_ptr_t)(uintptr_t)(sb + 2048u), 16, fv[2], feed.so, 0, 0);
+        feed.so += (unsigned)(8 * HWl * 4);
     };
 
     int cur = wave, nxt = next_unit();
-    dma_chunk(cur, 0);
-    dma_chunk(cur, 1);
+    WinoPlace cu = place(cur), nx = cu;
+    const unsigned char* nx_img = image(cu.b);
+    feed_unit(cu, nx_img);
+    dma_next(0);
+    dma_next(1);
+    if (nxt < total_units) {
+        nx = place(nxt);
+        nx_img = image(nx.b);
+    }
 
     const f32x2 c7525 = {0.75f, 0.25f}, c2575 = {0.25f, 0.75f};
     f32x4 acc[16][NCB];
     while (cur < total_units) {
         // this unit's place in the image: which of the patch's border rows / columns lie outside the up-sampled image
-        const int t = tile_first + (cur >> 3) * gstride;
-        const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
-        const int y0 = ty * WN_TH + 2 * (cur & 7), x0 = tx * WN_TW;
+        const int b = cu.b, y0 = cu.y0, x0 = cu.x0;
         const bool top = y0 == 0, bottom = y0 + 2 == H;
         const bool left = x0 == 0 && n == 0, right = x0 + WN_TW == W && n == 15;      // (per lane)
 #pragma unroll
@@ -1174,8 +1266,11 @@ __global__ __launch_bounds__(WN_THREADS, 1) void conv_wino_up_kernel(const WinoU
                     for (int m = 0; m < 3; ++m) x[r][m] = ip[r * WU_ROWF + m];
                 if (s == 1) {
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    if (c + 2 < NCH) dma_chunk(cur, c + 2);
-                    else if (nxt < total_units) dma_chunk(nxt, c + 2 - NCH);
+                    if (c + 2 < NCH) dma_next(c & 1);
+                    else if (nxt < total_units) {
+                        if (c + 2 == NCH) feed_unit(nx, nx_img);      // (the hand-over: cur's last chunk is on its way)
+                        dma_next(c & 1);
+                    }
                 }
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {      // bilinear clamp of the columns left / right of the image
@@ -1228,7 +1323,14 @@ __global__ __launch_bounds__(WN_THREADS, 1) void conv_wino_up_kernel(const WinoU
             wino_epilogue<NCB, 0>(acc, bias2, floor_v, ry, ry, st0, st1, so_t, so_t, HW);
         }
         cur = nxt;
-        if (cur < total_units) nxt = next_unit();
+        cu = nx;
+        if (cur < total_units) {
+            nxt = next_unit();
+            if (nxt < total_units) {
+                nx = place(nxt);
+                nx_img = image(nx.b);
+            }
+        }
     }
 }
 
@@ -1304,39 +1406,48 @@ __global__ __launch_bounds__(WN_THREADS, 1) void conv_wino16_up_kernel(const Win
         return (int)__builtin_amdgcn_readfirstlane(u);
     };
 
-    auto dma_chunk = [&](int unit, int c, int slot) {       // the four low-resolution rows under unit `unit`, chunk c (4 channels) -> slot
-        const int t = tile_first + (unit >> 3) * gstride;
-        const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
-        const int i = (ty * W6_TH >> 1) + 2 * (unit & 7), j0 = tx * (WN_TW / 2);
+    // the unit contexts: `cu` the place of the unit being computed, `nx` the place and the image of the unit taken after it, `feed` the DMA cursor (in `cur`
+    // until its last chunk is issued, then in `nxt`)
+    auto place = [&](int unit) { return wino_place(tile_first + (unit >> 3) * gstride, unit & 7, tiles_x, tiles_y, W6_TH, 4); };
+    auto image = [&](int b) { return reinterpret_cast<const unsigned char*>(a.x + (long long)b * a.x_bs) - lead; };
+    WinoFeed1 feed;
+    unsigned fv[2];                         // the lane's offsets for the unit being fetched
+    auto feed_unit = [&](WinoPlace p, const unsigned char* img) {
+        const int i = p.y0 >> 1, j0 = p.x0 >> 1;      // the unit's first low-resolution row and column
         const unsigned em = (i == 0 ? 1u : 0u) | (i + 2 == Hl ? 2u : 0u) | (j0 == 0 ? 4u : 0u) | (j0 + WN_TW / 2 == Wl ? 8u : 0u);
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(a.x + (long long)b * a.x_bs) - lead), 0, x_img, 0x00020000);
-        const unsigned so = (unsigned)((c * 4 * HWl + i * Wl + j0) * 4);
-        const unsigned sb = ring0 + (unsigned)(slot * WV_SLOT_BYTES);
-        unsigned v[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             unsigned o = rel[j];
             if (edge[j] & em & 1u) o += (unsigned)(Wl * 4);       // (bilinear clamp: the row above the image is row 0, the row below it the last row)
             if (edge[j] & em & 2u) o -= (unsigned)(Wl * 4);
-            v[j] = (edge[j] & em & 12u) ? 0x80000000u : o;
+            fv[j] = (edge[j] & em & 12u) ? 0x80000000u : o;
         }
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(uintptr_t)sb, 16, v[0], so, 0, 0);
-        if (lane < 32) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(uintptr_t)(sb + 1024u), 16, v[1], so, 0, 0);
+        feed.enter(img, x_img, (unsigned)((i * Wl + j0) * 4));
+    };
+    auto dma_next = [&](int slot) {       // the four low-resolution rows under the cursor's unit, its next chunk (4 channels) -> slot
+        const unsigned sb = ring0 + (unsigned)(slot * WV_SLOT_BYTES);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(feed.rx, (lds_ptr_t)(uintptr_t)sb, 16, fv[0], feed.so, 0, 0);
+        if (lane < 32) __builtin_amdgcn_raw_ptr_buffer_load_lds(feed.rx, (lds_ptr_t)(uintptr_t)(sb + 1024u), 16, fv[1], feed.so, 0, 0);
+        feed.so += (unsigned)(4 * HWl * 4);
     };
 
     int cur = wave, nxt = next_unit();
     int g = 0;
-    dma_chunk(cur, 0, 0);
-    dma_chunk(cur, 1, 1);
+    WinoPlace cu = place(cur), nx = cu;
+    const unsigned char* nx_img = image(cu.b);
+    feed_unit(cu, nx_img);
+    dma_next(0);
+    dma_next(1);
+    if (nxt < total_units) {
+        nx = place(nxt);
+        nx_img = image(nx.b);
+    }
 
     const f32x2 c7525 = {0.75f, 0.25f}, c2575 = {0.25f, 0.75f};
     f32x4 acc[2][16][1];
     const unsigned char* ringp = reinterpret_cast<const unsigned char*>(smem) + wbytes + wave * WV_RING_BYTES;
     while (cur < total_units) {
-        const int t = tile_first + (cur >> 3) * gstride;
-        const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
-        const int y0 = ty * W6_TH + 4 * (cur & 7), x0 = tx * WN_TW;
+        const int b = cu.b, y0 = cu.y0, x0 = cu.x0;
         const bool top = y0 == 0, bottom = y0 + 4 == H;
         const bool left = x0 == 0 && n == 0, right = x0 + WN_TW == W && n == 15;
         auto step = [&](int c, auto first) {
@@ -1350,8 +1461,10 @@ __global__ __launch_bounds__(WN_THREADS, 1) void conv_wino16_up_kernel(const Win
 #pragma unroll
                 for (int m = 0; m < 3; ++m) x[r][m] = ip[r * WU_ROWF + m];
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (c + 2 < nchunks) dma_chunk(cur, c + 2, slot);
-            else if (nxt < total_units) dma_chunk(nxt, c + 2 - nchunks, slot);
+            if (c + 2 < nchunks || nxt < total_units) {
+                if (c + 2 == nchunks) feed_unit(nx, nx_img);      // (the hand-over: cur's last chunk is on its way)
+                dma_next(slot);
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 x[r][0] = left ? x[r][1] : x[r][0];
@@ -1393,7 +1506,14 @@ __global__ __launch_bounds__(WN_THREADS, 1) void conv_wino16_up_kernel(const Win
             }
         }
         cur = nxt;
-        if (cur < total_units) nxt = next_unit();
+        cu = nx;
+        if (cur < total_units) {
+            nxt = next_unit();
+            if (nxt < total_units) {
+                nx = place(nxt);
+                nx_img = image(nx.b);
+            }
+        }
     }
 }
 
